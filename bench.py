@@ -11,8 +11,14 @@ round-robin (pvnet_amd.distributed.shard: weak scaling), one RCCL all_gather
 of every image's keypoints in stream order (gather_results) at the end of
 the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--per-step M]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--per-step M] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline figure needs: resident fields, warm-up,
+the K timed steps, DIR/keypoints.npy (the last timed step's keypoints) when
+asked, the line.  --full adds every other leg after it: the checks of the
+timed outputs, the other stream configurations, per-kernel timings and
+rooflines, the end-to-end configs and the CPU baseline (--skip-* choose).
 
 With --gpus N > 1 and no torchrun environment (WORLD_SIZE unset) the process
 starts the N ranks itself (launch_ranks: one child per GPU carrying RANK /
@@ -109,6 +115,16 @@ def parse():
     ap.add_argument("--hn", type=int, default=512, help="round_hyp_num (DEMO:55 / TRAIN:141)")
     ap.add_argument("--inflight", type=int, default=8,
                     help="images in flight: consecutive images alternate over this many HIP streams (own workspaces)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline stream also run every other leg (checks of the timed outputs against "
+                         "the generating keypoints and the golden fixtures, stream_batched4, configs[3]/[4] streams, "
+                         "per-kernel timings, latency, rooflines, end-to-end configs, CPU baseline); the --skip-* "
+                         "options select among them.  Without it the run sets up, warms up, times --steps steps, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed to DIR/keypoints.npy: the "
+                         "[n_gpus * per-step, 9, 2] float32 keypoints of the step's frames in stream order (the "
+                         "inputs and seeds are the same from run to run)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU-baseline sample")
     ap.add_argument("--skip-cpu", action="store_true")
     ap.add_argument("--skip-e2e", action="store_true")
@@ -498,6 +514,14 @@ def stream_order_error(allkp, ws, nfields):
     return float(np.abs(got - ref[np.arange(got.shape[0]) % (nfields * ws)]).max())
 
 
+def dump_outputs(path, allkp, last):
+    """--dump-outputs: the last timed step's results, the final ``last``
+    images of the gathered stream (image i of step k on rank r is stream
+    image (k * M + i) * ws + r), as path/keypoints.npy, float32."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "keypoints.npy"), allkp[allkp.shape[0] - last:].cpu().numpy().astype(np.float32))
+
+
 def dry_run(args, ws, rank):
     """--dry-run (CPU, gloo): the launcher, the shard, the timed region's
     barriers, the gather, the max over ranks and the stream-order check, with
@@ -531,7 +555,9 @@ def dry_run(args, ws, rank):
                 "stream_order_max_err_px": err, "stream_order_ok": err == 0.0,
                 "rank_cpus": args.rank_cpus_all, "rank_cpus_source": args.rank_cpus[1]}
         assert line["n_gpus"] == args.gpus
-        if not args.skip_cpu:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, allkp, ws * M)
+        if args.full and not args.skip_cpu:
             line["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         print(json.dumps(line), flush=True)
     if ws > 1:
@@ -558,6 +584,17 @@ def main():
     assert all(field_seed(rank + ws * j, ws, NF) == 1234 + rank + ws * (j % NF) for j in range(4 * NF))
     hs = {}
     elapsed, local, works, s, allkp = run_stream(args, ws, rank, dev, segs, vers, K, 0, stats=hs)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, allkp, ws * M)
+    if not args.full:
+        # the plain run: the headline figure only (every other leg and check is --full's)
+        if rank == 0:
+            report(args, ws, dict(elapsed=elapsed, tn=tn, n_images=n_images,
+                                  host_ms_per_replay=hs["host_replay_s"] / K * 1e3), None, dev)
+        if ws > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # every gathered image against its field's generating keypoints: a result
     # in the wrong stream slot would be tens of pixels off
     order_err = stream_order_error(allkp, ws, NF)
@@ -1285,9 +1322,11 @@ def library_config():
 
 
 def report(args, ws, res, final_err, dev):
-    K, M = args.steps, args.per_step
-    elapsed = res["elapsed"]
-    value = res["n_images"] / elapsed
+    if not args.full:
+        line = headline(args, ws, res)
+        assert line["n_gpus"] == args.gpus, (line["n_gpus"], args.gpus)
+        print(json.dumps(line), flush=True)
+        return
     tn = res["tn"]
     vote_ms = float(np.mean(res["vote_ms"]))
     pairs = float(args.hn * VN * tn)                # per launch: one launch votes one batch-1 frame
@@ -1319,30 +1358,8 @@ def report(args, ws, res, final_err, dev):
                    "(cx, cy, nx, ny) operands), not 8; since round 6 the k_compact launch also makes the "
                    "frame's hypotheses (its first blocks, PVV_HYPFUSE), so this time includes that work (U2's "
                    "input, not U3's bytes); traffic = the two kernels' PMC bytes (%s)" % PMC_FILE)
-    line = {
-        "metric": "images/sec (480x640, 9 kp) vote->keypoint",
-        "value": round(value, 2),
-        "unit": "images/sec",
-        "n_gpus": ws,
-        "steps": K,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / K * 1e3, 5),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic S(seed) fields (SURVEY 8(d)): disk r=97.5 -> 29,861 fg px, 9 kp, 0.05 rad noise, "
-                "20%% outliers; network-layout seg_pred/vertex_pred f32 resident in HBM, %d distinct fields per "
-                "GPU cycled (%.0f MB, beyond the 256 MiB Infinity Cache)" % (args.fields, args.fields * 24.576),
-        "config": {"workload": "stream of LINEMOD-cat-sized batch-1 frames (configs[1]'s voting layer): "
-                               "ransac_voting_layer_v3 (hn=%d, thr=0.99) from seg_pred/vertex_pred; one step = one "
-                               "hipGraph replay voting %d frames per GPU, %d in flight on separate streams; "
-                               "images sharded round-robin over ranks, one gather of all keypoints at the end"
-                               % (args.hn, M, max(1, args.inflight)),
-                   "global_batch": M * ws, "per_gpu_batch_per_step": M, "image": [H, W], "keypoints": VN,
-                   "round_hyp_num": args.hn, "foreground_px": int(tn),
-                   "parallelism": "dp%d (images sharded round-robin, RCCL all_gather of keypoints)" % ws,
-                   "images_in_flight": max(1, args.inflight), "stream_images": res["n_images"]},
+    line = headline(args, ws, res)
+    line.update({
         "roofline": None,
         "roofline_vote_count": vc,
         "roofline_compaction": rc,
@@ -1350,12 +1367,7 @@ def report(args, ws, res, final_err, dev):
         "stream_order_max_err_px": round(res["order_err"], 5),
         "stream_order_ok": res["order_err"] <= 5.0,
         "latency_ms_per_image": round(res["latency_ms"], 5),
-        "host_ms_per_replay": round(res["host_ms_per_replay"], 4),
-        "kernel_nodes_per_frame": kernel_nodes(1, args.hn),
-        "rank_cpus": args.rank_cpus_all,
-        "rank_cpus_source": args.rank_cpus[1],
-        "library": library_config(),
-    }
+    })
     if res.get("batched") is not None:
         line["stream_batched4"] = res["batched"]
     if res.get("config3") is not None:
@@ -1406,6 +1418,44 @@ def report(args, ws, res, final_err, dev):
         line["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
     assert line["n_gpus"] == args.gpus, (line["n_gpus"], args.gpus)
     print(json.dumps(line), flush=True)
+
+
+def headline(args, ws, res):
+    """The line of a plain run: the headline figure, how it was taken and
+    with which library; report() adds --full's legs to it."""
+    K, M = args.steps, args.per_step
+    elapsed, tn = res["elapsed"], res["tn"]
+    value = res["n_images"] / elapsed
+    return {
+        "metric": "images/sec (480x640, 9 kp) vote->keypoint",
+        "value": round(value, 2),
+        "unit": "images/sec",
+        "n_gpus": ws,
+        "steps": K,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / K * 1e3, 5),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic S(seed) fields (SURVEY 8(d)): disk r=97.5 -> 29,861 fg px, 9 kp, 0.05 rad noise, "
+                "20%% outliers; network-layout seg_pred/vertex_pred f32 resident in HBM, %d distinct fields per "
+                "GPU cycled (%.0f MB, beyond the 256 MiB Infinity Cache)" % (args.fields, args.fields * 24.576),
+        "config": {"workload": "stream of LINEMOD-cat-sized batch-1 frames (configs[1]'s voting layer): "
+                               "ransac_voting_layer_v3 (hn=%d, thr=0.99) from seg_pred/vertex_pred; one step = one "
+                               "hipGraph replay voting %d frames per GPU, %d in flight on separate streams; "
+                               "images sharded round-robin over ranks, one gather of all keypoints at the end"
+                               % (args.hn, M, max(1, args.inflight)),
+                   "global_batch": M * ws, "per_gpu_batch_per_step": M, "image": [H, W], "keypoints": VN,
+                   "round_hyp_num": args.hn, "foreground_px": int(tn),
+                   "parallelism": "dp%d (images sharded round-robin, RCCL all_gather of keypoints)" % ws,
+                   "images_in_flight": max(1, args.inflight), "stream_images": res["n_images"]},
+        "host_ms_per_replay": round(res["host_ms_per_replay"], 4),
+        "kernel_nodes_per_frame": kernel_nodes(1, args.hn),
+        "rank_cpus": args.rank_cpus_all,
+        "rank_cpus_source": args.rank_cpus[1],
+        "library": library_config(),
+    }
 
 
 if __name__ == "__main__":

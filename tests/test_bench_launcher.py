@@ -24,7 +24,7 @@ def _run(*extra, env_extra=None, timeout=240):
 
 @pytest.mark.parametrize("n", [2, 3])
 def test_launcher_gpus_n_gloo(n):
-    p = _run("--gpus", str(n))
+    p = _run("--gpus", str(n), "--full")           # the CPU baseline is one of --full's legs
     assert p.returncode == 0, p.stderr[-3000:]
     # one JSON line, from rank 0 only (gloo itself prints a connection note)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -41,6 +41,30 @@ def test_launcher_gpus_1_single_process():
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
     assert line["n_gpus"] == 1 and line["stream_order_ok"]
+
+
+def test_plain_run_line_and_dump_outputs(tmp_path):
+    """A plain run (no --full) prints the headline keys and no CPU baseline;
+    --dump-outputs writes the last step's keypoints of every rank's frames in
+    stream order, float32, the same from run to run."""
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        p = _run("--gpus", "2", "--dump-outputs", str(tmp_path / d))
+        assert p.returncode == 0, p.stderr[-3000:]
+        line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in line
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and "cpu_baseline" not in line
+        assert os.listdir(tmp_path / d) == ["keypoints.npy"]
+        outs.append(np.load(tmp_path / d / "keypoints.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (2 * 10, 9, 2)
+    np.testing.assert_array_equal(outs[0], outs[1])
+    # the last step's frames: stream images 40..59, image i from S(field_seed(i))
+    import bench
+    from pvnet_amd import synth
+    ref = np.stack([synth.field_keypoints(bench.field_seed(i, 2, 4)) for i in range(40, 60)]).astype(np.float32)
+    np.testing.assert_array_equal(outs[0], ref)
 
 
 def test_world_size_mismatch_fails():
@@ -65,7 +89,7 @@ def test_launcher_two_ranks_on_the_device():
     line with n_gpus 2 and every gathered image in its stream slot."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--share-device", "--steps", "2",
-           "--warmup", "1", "--per-step", "16", "--fields", "4", "--skip-e2e", "--skip-u1", "--skip-u4",
+           "--warmup", "1", "--per-step", "16", "--fields", "4", "--full", "--skip-e2e", "--skip-u1", "--skip-u4",
            "--skip-cpu"]
     p = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=580)
     assert p.returncode == 0, p.stderr[-3000:]

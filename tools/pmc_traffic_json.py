@@ -25,7 +25,7 @@ if len(sys.argv) > 5:
         write[k + "_evd"] = v
 out = {
     "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of "
-              "`python3 bench.py --steps 5 --warmup 2 --skip-cpu --skip-e2e --skip-config3 --skip-u4` (the pipeline and "
+              "`python3 bench.py --steps 5 --warmup 2 --full --skip-cpu --skip-e2e --skip-config3 --skip-u4` (the pipeline and "
               "U1 phases), mean per dispatch; *_evd: `python3 tools/u4_probe.py` (U4 alone) (tools/prof_bench.sh "
               "with PMC=1)",
     "correction": "gfx950: FETCH_SIZE counts half the bytes of wide streaming reads (MI355X_MICROARCH.md HBM "

@@ -20,7 +20,7 @@ d = np.array([(e - s) / 1e3 for s, e in ev])
 t = ev[-n:]
 line = json.loads(open(sys.argv[2]).read())
 out = {
-    "source": "rocprofv3 --kernel-trace of `python3 bench.py --gpus 1 --steps 20 --warmup 5` (tools/prof_bench.sh)",
+    "source": "rocprofv3 --kernel-trace of `python3 bench.py --gpus 1 --steps 20 --warmup 5 --full` (tools/prof_bench.sh)",
     "launches_all": len(ev), "mean_us_all": round(float(d.mean()), 3),
     "timed_launches": n, "timed_mean_us": round(float(d[-n:].mean()), 3),
     "timed_median_us": round(float(np.median(d[-n:])), 3),

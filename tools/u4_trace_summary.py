@@ -26,7 +26,7 @@ for r in rows:
 n = int(u4["samples"])
 d = np.array(pairs[-n:])
 out = {
-    "source": "rocprofv3 --kernel-trace of `python3 bench.py --gpus 1 --steps 20 --warmup 5` (tools/prof_bench.sh)",
+    "source": "rocprofv3 --kernel-trace of `python3 bench.py --gpus 1 --steps 20 --warmup 5 --full` (tools/prof_bench.sh)",
     "u4_calls_found": len(pairs), "timed_calls": n,
     "vote_median_us": round(float(np.median(d[:, 0])), 3), "vote_mean_us": round(float(d[:, 0].mean()), 3),
     "evd_reduce_median_us": round(float(np.median(d[:, 1])), 3),
