@@ -27,6 +27,7 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <array>
+#include <atomic>
 
 #include <algorithm>
 #include <type_traits>
@@ -292,19 +293,6 @@ __device__ __forceinline__ int wave_sum_i(int x) {
     const auto r32 = __builtin_amdgcn_permlane32_swap(x, x, false, false);
     return (int)(r32[0] + r32[1]);
 }
-// inclusive prefix sum over the wave by DPP: row_shr 1/2/4/8 within each
-// 16-lane row (bound_ctrl: lanes past the row start add 0), then row_bcast15
-// (rows 1, 3) and row_bcast31 (rows 2, 3) -- no ds_bpermute round trips
-// (the __shfl_up form is six serial LDS latencies)
-__device__ __forceinline__ int wave_incl_scan_i(int x) {
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);
-    return x;
-}
 __device__ __forceinline__ double wave_sum_d(double x) {
     for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
     return x;
@@ -447,9 +435,6 @@ struct VertexView {
     int32_t extent;     // bytes spanned by one image's [h,w,vn,2] view (< 2^31: buffer-load range)
 };
 
-#ifndef PVV_COMPACT_SKIP
-#define PVV_COMPACT_SKIP 1   // k_compact blocks without foreground exit at once
-#endif
 constexpr int kCompactKp = 12;   // keypoints whose vertex loads a compaction thread keeps in flight at once
 constexpr uint64_t kLookbackSpin = 20000;   // s_memrealtime ticks (100 MHz): 200 us
 __device__ int g_lb_self;   // debug (pv_debug_lookback_self): every look-back count worked out by the waiter
@@ -466,13 +451,11 @@ __device__ __forceinline__ void compact_chunk(const VertexView &vx, int H, int W
     const int64_t P = (int64_t)H * W;
     const int wid = threadIdx.x / 64, lane = lane_id();
     cstamp(blk, 0);
-#if PVV_COMPACT_SKIP
     // a block without foreground has nothing to store; only blocks 0 and
     // nblk - 1 (which write tn / fgtot) run on.  The downsampling look-back
     // below takes such a predecessor's kept count as 0 from its k_fg_count
     // count, without waiting for it.
     if (blk != 0 && blk != nblk - 1 && blkcnt[b * nblk + blk] == 0) return;
-#endif
     // one round trip: this wave's foreground ballot (k_fg_count) beside the
     // image's per-block counts (the total and this block's row-major offset)
     const uint64_t fw = fgbits[((int64_t)b * nblk + blk) * 4 + wid];
@@ -571,9 +554,7 @@ __device__ __forceinline__ void compact_chunk(const VertexView &vx, int H, int W
         // so no thread waits longer than kLookbackSpin in all
         const uint64_t t_dead = __builtin_amdgcn_s_memrealtime() + kLookbackSpin;
         for (int j = threadIdx.x; j < blk; j += 256) {
-#if PVV_COMPACT_SKIP
             if (blkcnt[b * nblk + j] == 0) continue;   // no foreground: kept 0 (the block may not publish)
-#endif
             int v = self_all ? 0 : ld_agent(&agg[j]);
             if (v == 0 && !self_all)
                 while ((v = ld_agent(&agg[j])) == 0 && __builtin_amdgcn_s_memrealtime() < t_dead)
@@ -662,9 +643,6 @@ __device__ __forceinline__ void compact_chunk(const VertexView &vx, int H, int W
 // ballots), one kernel fewer in the call's chain: a k_hyp_gen launch costs
 // the batch-1 stream ~9 % (profiles/r06/ablation.txt).
 // ==========================================================================
-#ifndef PVV_HYP_FASTSEARCH
-#define PVV_HYP_FASTSEARCH 0   // 1: compact_hyp with a DPP wave scan and an 8-ary chunk search (bit-identical; measured neutral)
-#endif
 constexpr int kHypMaxChunks = 1536;   // chunks per image the fused hypotheses handle (LDS prefix); more: k_hyp_gen
 struct HypGen {
     int nhb;                    // hypothesis blocks per image (0: none, k_hyp_gen runs)
@@ -732,16 +710,12 @@ __device__ void compact_hyp(const VertexView &vx, int H, int W, int nblk, const 
 #pragma unroll
         for (int k = 0; k < 6; ++k) run += v[k];
         // inclusive wave scan of run (row shifts + row broadcasts)
-#if PVV_HYP_FASTSEARCH
-        const int x = wave_incl_scan_i(run);
-#else
         int x = run;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
             const int y = __shfl_up(x, o);
             if (lane_id() >= o) x += y;
         }
-#endif
         __syncthreads();
         if (lane_id() == 63) sh[threadIdx.x / 64] = x;
         __syncthreads();
@@ -821,27 +795,6 @@ __device__ void compact_hyp(const VertexView &vx, int H, int W, int nblk, const 
 #pragma unroll
     for (int e = 0; e < 2; ++e) {                  // the last chunk with pre <= t (never an empty one)
         int lo = 0, hi = nblk - 1;
-#if PVV_HYP_FASTSEARCH
-        // 8-ary: seven pivots read together per step (4 dependent LDS trips
-        // for 1,200 chunks instead of 11); the same index as the bisection
-        while (hi - lo >= 8) {
-            int pv[7], cnt = 0;
-#pragma unroll
-            for (int k = 0; k < 7; ++k) pv[k] = lo + (int)(((int64_t)(hi - lo) * (k + 1) + 7) / 8);
-            int vv[7];
-#pragma unroll
-            for (int k = 0; k < 7; ++k) vv[k] = pre[pv[k]];
-#pragma unroll
-            for (int k = 0; k < 7; ++k) cnt += vv[k] <= t[e] ? 1 : 0;
-            int nlo = lo, nhi = hi;
-#pragma unroll
-            for (int k = 0; k < 7; ++k) {
-                if (cnt == k + 1) nlo = pv[k];
-                if (cnt == k) nhi = pv[k] - 1;
-            }
-            lo = nlo; hi = nhi;
-        }
-#endif
         while (lo < hi) {
             const int mid = (lo + hi + 1) >> 1;
             if (pre[mid] <= t[e]) lo = mid; else hi = mid - 1;
@@ -955,14 +908,6 @@ __global__ __launch_bounds__(256) void k_compact(MaskView, VertexView vx, int H,
 // plain PODs read through the constant address space -> s_load (scalar) loads
 struct alignas(16) F4 { float x, y, z, w; };
 struct alignas(8) F2 { float x, y; };
-// a pointer the compiler can see is wave-uniform (so loads through it become s_load)
-template <typename T>
-__device__ __forceinline__ T *uptr(T *p) {
-    uint64_t v = (uint64_t)p;
-    uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return (T *)(((uint64_t)hi << 32) | lo);
-}
 
 struct VoteArgs {
     const float4 *pex;          // PREPPED: exact data (cx, cy, nx, ny), same layout
@@ -1229,15 +1174,11 @@ __device__ __forceinline__ void vote_segment(const VoteArgs &a, VoteSlab<PREPPED
     for (int i = 0; i < kHypLane; ++i) {
         const int h = hg * kGroup + i * kWave + lane;
         const bool hl = h < a.nh;
-#ifndef PVVOTE_ABLATE_HYP
         // the pipeline (PREPPED) makes its hypotheses here: every block of
         // (b, v, group) intersects the same pixel pairs, the one whose range
         // starts at pixel 0 stores them (reference layout, for the refine /
         // EVD stages and the diagnostics); the API path reads the caller's
         const float2 hv = item_hyp<PREPPED, PREPPED>(a, b, v, h, hl, n, PREPPED && ts == 0);
-#else
-        const float2 hv = make_float2(300.f + 0.37f * lane + 0.11f * v, 200.f + 0.23f * i + 0.5f * hg);
-#endif
         he_set(i, hv);
         const bool fin = isfinite(hv.x) && isfinite(hv.y);    // non-finite: never an inlier
         hxo[i] = hl && fin && hyp_exact_only(hv.x, hv.y);
@@ -1492,11 +1433,7 @@ __device__ __forceinline__ void vote_segment(const VoteArgs &a, VoteSlab<PREPPED
             };
             // the slab past np holds never-voting pixels (negative z, never in
             // the band), so the loop runs whole 8-pixel iterations
-#ifdef PVVOTE_ABLATE_LOOP
-            const int nit = 0;
-#else
             const int nit = (np + 7) >> 3;
-#endif
             F4 a0 = stage[0], a1 = stage[1], a2 = stage[2], a3 = stage[3];
             if (PVV_TRACE_ON(a) && tloop == 0) tloop = __builtin_amdgcn_s_memrealtime();   // (debug traces only)
             for (int it = 0; it < nit; ++it) {
@@ -1521,9 +1458,7 @@ __device__ __forceinline__ void vote_segment(const VoteArgs &a, VoteSlab<PREPPED
                     hm &= hm - 1;
                     if ((j >> 6) != kq) { kq = j >> 6; set_band(kq); }
                     ++nfix;
-#ifndef PVVOTE_ABLATE_FIX   // (profiling ablation: band pairs keep the sign count's guess)
                     fix_step(j);
-#endif
                 }
             }
             // positives = pairs stepped - negatives (never-voting pixels and the
@@ -1573,11 +1508,7 @@ __device__ __forceinline__ void vote_segment(const VoteArgs &a, VoteSlab<PREPPED
 #pragma unroll
     for (int i = 0; i < kHypLane; ++i) {
         const int h = hg * kGroup + i * kWave + lane;
-#ifndef PVVOTE_ABLATE_ATOMIC
         if (h < a.nh && cnt[i]) atomicAdd(&cp[(int64_t)h * a.cnt_h], cnt[i]);
-#else
-        if (h < a.nh && cnt[i] == 0x7fffffff) cp[0] = 1;
-#endif
     }
 }
 
@@ -1649,13 +1580,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
     }
 }
 
+#ifdef PVV_PROFILE
+// profiling builds only (pv_debug_set_ablation bit 32): a launch that does nothing
+__global__ void k_abl_empty(int) {}
+#endif
+
 // Hypotheses once per launch (pipeline, hyp_pregen), one thread per
 // (image, hypothesis, keypoint): the pixel pair (the caller's idxs or the
 // counter RNG, RV:553) and its intersection (KU:11-49), stored in the
 // reference layout and keypoint-major; images without a vote are left alone.
-// profiling ablations only (pv_debug_set_ablation bit 32): a launch that does nothing
-__global__ void k_abl_empty(int) {}
-
 __global__ __launch_bounds__(256) void k_hyp_gen(VoteArgs a) {
     const int64_t per = (int64_t)a.nh * a.vn;
     const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1707,27 +1640,6 @@ constexpr int kMB = 16;                        // pixels per MFMA batch (32 rows
 #ifndef PVM_QUEUE
 #define PVM_QUEUE 128
 #endif
-#ifndef PVM_DMAX
-// 1: the hot-loop band's reference-error term against the sub-chunk box's
-// farthest pixel instead of B (6 % fewer flagged MFMAs on S(1234), but the
-// stream measured 2 % slower: profiles/r06/vote_band_ab.txt)
-#define PVM_DMAX 0
-#endif
-#ifndef PVM_BANDV
-#define PVM_BANDV 2     // band re-check: 2 one FMA a pair to find candidates (round 6), 1 the full per-pair bound (round 5)
-#endif
-#if PVM_DMAX && PVM_BANDV >= 2
-#error "PVM_BANDV 2 derives G from the hot-loop bound, which PVM_DMAX changes"
-#endif
-#ifndef PVM_ONEBAR
-#define PVM_ONEBAR 0    // 1: k_vote_mfma<PREPPED> stages a sub-chunk with one barrier (origin = its first / last records' midpoint)
-#endif
-#ifndef PVM_HOTPRIO
-#define PVM_HOTPRIO 3   // k_vote_mfma's hot-loop issue priority (the rest of the kernel runs at 3)
-#endif
-#ifndef PVM_BANDK
-#define PVM_BANDK 1     // flagged MFMAs re-checked this many at a time (2 measured the same as 1)
-#endif
 // pixels per sub-chunk: a unit's range (~350 px at configs[1]) in one; 352
 // (with a 128-entry band queue) keeps the block's LDS under 40 KiB, so a
 // fourth block -- the next image's -- fits beside a launch's three per CU
@@ -1739,6 +1651,10 @@ constexpr int kMSet = 4;                       // 32-hypothesis column sets per 
 constexpr float kMHypMax = 8.0e6f;             // |hx|, |hy| above -> exact-only (keeps s >= 2^-9)
 constexpr float kMRMax = 30000.f;              // sub-chunk radius above -> exact sub-chunk (fp16 range of b)
 constexpr int kMQueue = PVM_QUEUE;             // band pairs queued per wave before a reference pass
+// flagged MFMAs re-checked at a time (2 measured the same as 1).  The re-check
+// loop stays written over kMBandK entries, the form the measured kernel was
+// compiled from: the scalar form is equivalent but schedules differently
+constexpr int kMBandK = 1;
 
 template <bool PREPPED>
 struct MSlab {
@@ -1759,13 +1675,6 @@ __device__ __forceinline__ uint4 form_row(float ax, float ay, float b) {
     return make_uint4(pack_h2(axh, axh), pack_h2(axl, ayh), pack_h2(ayh, ayl), pack_h2(bh, bl));
 }
 
-#ifndef PVM_ALIGNED
-// 1: one-image launches split along (keypoint, group) segments -- no block
-// pays a second segment's prologue: the launch alone 28.1 -> 25.4 us span
-// (tools/vote_trace.py), but sequential latency only 48.3-48.7 -> 48.0-48.2 us
-// and the stream 54.2k -> 53.3-53.6k images/s (tools/ab_libs.sh, two rounds)
-#define PVM_ALIGNED 0
-#endif
 #ifndef PVM_WPE
 // waves per SIMD the registers are sized for.  Round 2: 3 (152 VGPRs; 4 then
 // spilled across the hot loop): 40.4k -> 41.5k images/s.  Round 6: the kernel
@@ -1799,25 +1708,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
     uint32_t total = 0;
     for (int b = 0; b < a.b; ++b) total += (uint32_t)(a.vn * ggn) * (uint32_t)tn_at(a, b);
     uint32_t lo, hi;
-    const uint32_t nsegs = (uint32_t)(a.vn * ggn);
-    if (PVM_ALIGNED && a.b == 1 && a.rw[0] == 0 && nunits >= nsegs) {
-        // one image: every block inside one (keypoint, 512-hypothesis group)
-        // segment -- nunits / nsegs blocks per segment, the first nunits % nsegs
-        // segments one more -- so that no block pays a second segment's
-        // prologue (the launch's last waves were such blocks); the shares
-        // differ by at most one block's part of a segment (< 1 %)
-        const uint32_t base = nunits / nsegs, extra = nunits - base * nsegs;
-        uint32_t sg, k, nb;
-        if ((uint32_t)unit < extra * (base + 1)) {
-            sg = (uint32_t)unit / (base + 1); k = (uint32_t)unit - sg * (base + 1); nb = base + 1;
-        } else {
-            const uint32_t u2 = (uint32_t)unit - extra * (base + 1);
-            sg = extra + u2 / base; k = u2 - (u2 / base) * base; nb = base;
-        }
-        const uint64_t n = (uint64_t)tn_at(a, 0);
-        lo = sg * (uint32_t)n + (uint32_t)(k * n / nb);
-        hi = sg * (uint32_t)n + (uint32_t)((k + 1) * n / nb);
-    } else if (a.rw[0] > 0 && nunits % (a.rw[3] > 0 ? 4 : 3) == 0) {
+    if (a.rw[0] > 0 && nunits % (a.rw[3] > 0 ? 4 : 3) == 0) {
         round_share(total, nunits, (uint32_t)unit, a.rw, &lo, &hi);
     } else {
         even_share(total, nunits, (uint32_t)unit, &lo, &hi);
@@ -1845,19 +1736,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
         // ---- segment: pixels [ts, te) of (b, v) against hypotheses hg*128 .. +127 ----
         c_mark = cyc();
         F4 L[kMSlots];
-        // (PVM_ONEBAR: the sub-chunk's first and last records, whose midpoint is
-        // the origin -- row-major compacted records: a strip of rows)
-        float fx0 = 0.f, fy0 = 0.f, fx1 = 0.f, fy1 = 0.f;
         auto load_px = [&](int s0, int np) {
 #pragma unroll
             for (int k = 0; k < kMSlots; ++k) {
                 const int t = k * 256 + wid * kWave + lane;
                 L[k] = F4{0.f, 0.f, 0.f, 0.f};
                 if (t < np) L[k] = pixel_exact<PREPPED>(a, b, v, s0 + t);
-            }
-            if (PVM_ONEBAR && PREPPED) {
-                const F4 e0 = pixel_exact<PREPPED>(a, b, v, s0), e1 = pixel_exact<PREPPED>(a, b, v, s0 + np - 1);
-                fx0 = e0.x; fy0 = e0.y; fx1 = e1.x; fy1 = e1.y;
             }
         };
         load_px(ts, min(kMChunk, te - ts));
@@ -1966,22 +1850,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                     S.rows[tt >> 4][2 * (tt & 15) + 1] = ry;
                 }
             };
-            constexpr bool onebar = PVM_ONEBAR && PREPPED;
-            float ox = 0.f, oy = 0.f;
-            if constexpr (onebar) {
-                // One barrier per sub-chunk: the origin is the midpoint of the
-                // sub-chunk's first and last records (known to every thread
-                // before any reduction), the rows are written against it
-                // before the barrier, and the box reduction after it only
-                // measures R about that origin (an origin anywhere keeps every
-                // decision exact; a central one keeps R, so the band, small)
-                ox = floorf(0.5f * fx0 + 0.5f * fx1);
-                oy = floorf(0.5f * fy0 + 0.5f * fy1);
-                if (!(fabsf(ox) <= 1.6e7f && fabsf(oy) <= 1.6e7f)) { ox = 0.f; oy = 0.f; }
-                ox = __builtin_amdgcn_readfirstlane(ox);
-                oy = __builtin_amdgcn_readfirstlane(oy);
-                put_rows(ox, oy, !a.fast);
-            }
             // next sub-chunk's loads, in flight across the barriers and the hot loop
             if (s0 + kMChunk < te) load_px(s0 + kMChunk, min(kMChunk, te - s0 - kMChunk));
             __syncthreads();
@@ -1994,20 +1862,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                 cyl = fminf(cyl, Q.z); cyh = fmaxf(cyh, Q.w);
                 exq |= QB.exo[k];
             }
-            if constexpr (!onebar) {
-                ox = floorf(0.5f * cxl + 0.5f * cxh), oy = floorf(0.5f * cyl + 0.5f * cyh);
-                if (!(fabsf(ox) <= 1.6e7f && fabsf(oy) <= 1.6e7f)) { ox = 0.f; oy = 0.f; }
-            }
+            float ox = floorf(0.5f * cxl + 0.5f * cxh), oy = floorf(0.5f * cyl + 0.5f * cyh);
+            if (!(fabsf(ox) <= 1.6e7f && fabsf(oy) <= 1.6e7f)) { ox = 0.f; oy = 0.f; }
             const float axr = fmaxf(cxh - ox, ox - cxl), ayr = fmaxf(cyh - oy, oy - cyl);
             const float R = __builtin_amdgcn_sqrtf(fmaf(axr, axr, ayr * ayr)) * 1.00001f;
             // (the fp16 b operands reach max(tau, 1) R: tau u.c' for X, u x c' for Y)
             bool slow = !a.fast || exq != 0 || !(R * fmaxf(tau, 1.f) <= kMRMax);
             slow = __builtin_amdgcn_readfirstlane(slow);
             nslow += slow ? 1 : 0;
-            if constexpr (!onebar) {
-                put_rows(ox, oy, slow);
-                __syncthreads();
-            }
+            put_rows(ox, oy, slow);
+            __syncthreads();
             if (!slow) {
                 // ---- the hypotheses' B fragments and bands for this origin ----
                 // hypothesis j's scale s = 2^-k (|h' s| < 2^14) and bound B >=
@@ -2039,25 +1903,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                     h4f f = half ? h4f{yl_, yh_, sh, sh} : h4f{xh_, xl_, xh_, yh_};
                     if (!fj) f = h4f{(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
                     bf[j] = f;
-#if PVM_DMAX
-                    // the reference-error term against the farthest pixel the
-                    // sub-chunk's box allows, not B: D <= |(|h'x| + axr, |h'y| + ayr)|
-                    // <= |h'| + R (a strip of rows is wide, not tall: 15-30 %
-                    // smaller for hypotheses above or below it)
-                    const float ex = fabsf(hx) + axr, ey = fabsf(hy) + ayr;
-                    const float Dm = __builtin_amdgcn_sqrtf(fmaf(ex, ex, ey * ey)) * 1.0001f;
-                    gb[j] = fj ? (a.gzf * Bv + a.gzr * Dm) * s * 1.00001f : -1.f;
-#else
                     gb[j] = fj ? (a.gzf + a.gzr) * Bv * s * 1.00001f : -1.f;
-#endif
                 }
                 uint32_t neg[kMSet] = {0u, 0u, 0u, 0u};
                 uint64_t hm0 = 0, hm1 = 0;              // band hits: bit 4 p + set, batches 0-15 / 16-31
-#ifdef PVM_ABL_HOT
-                const int nb = 0;
-#else
                 const int nb = (np + kMB - 1) / kMB;
-#endif
                 const uint2 *arow = (const uint2 *)&S.rows[0][0];
                 // the lane's A fragment of batch p: row (col) of the batch's 32
                 // rows (pixel col>>1, form col&1), k half `half`
@@ -2091,12 +1941,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                 const f32x16 zero = {};
                 if (PVV_TRACE_ON(a) && tloop == 0) tloop = __builtin_amdgcn_s_memrealtime();
                 { const uint64_t t = cyc(); c_stage += t - c_mark; c_mark = t; }
-#if PVM_HOTPRIO < 3
-                // the hot loop below the kernel's other phases: a wave in its
-                // prologue, staging or band re-check (latency-bound chains of a
-                // few instructions) issues ahead of the co-resident hot loops
-                __builtin_amdgcn_s_setprio(PVM_HOTPRIO);
-#endif
                 h4f A = afrag(0);
                 f32x16 c0 = __builtin_amdgcn_mfma_f32_32x32x8f16(A, bf[0], zero, 0, 0, 0);
 #pragma unroll 1
@@ -2118,9 +1962,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                     if (p < 16) hm0 |= hbs; else hm1 |= hbs;
                     A = An;
                 }
-#if PVM_HOTPRIO < 3
-                __builtin_amdgcn_s_setprio(3);
-#endif
                 // positives = slots - negatives (padding and never-voting rows are negative)
 #pragma unroll
                 for (int j = 0; j < kMSet; ++j) cnt[j] += ((hfm >> j) & 1u) ? 8 * nb - (int)(neg[j] / 255u) : 0;
@@ -2130,11 +1971,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                 // D = |h - c| <= |x'| + |y'| = |X| / tau + |Y| (scaled by s;
                 // the forms' own errors, < gzm B s, add < 1e-3 of G), and the
                 // reference's sequence inside the band ----
-#ifdef PVM_ABL_FIX
-                nfix += __popcll(hm0) + __popcll(hm1);
-                hm0 = hm1 = 0;
-#endif
-#ifdef PVM_ABL_FIX_RT   // the same, decided at run time (the band code stays in the kernel)
+#ifdef PVV_PROFILE   // ablation bit 64: band pairs keep the sign count's guess (counts wrong)
                 if (a.rw[3] == 7777) hm0 = hm1 = 0;
 #endif
                 const float kx = a.gzr / tau * 1.0001f, ky = a.gzr * 1.0001f;
@@ -2155,7 +1992,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                     }
                     nq = 0;
                 };
-#if PVM_BANDV >= 2
                 // Each set's per-pair constant G = gzf B s (1.001), once: from
                 // the hot-loop bound gb = (gzf + gzr) B s (1.00001) with the
                 // same B and s, gb gzf / (gzf + gzr) 1.0011 >= gzf B s 1.001 --
@@ -2195,7 +2031,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                     mt = __builtin_elementwise_minimum(__builtin_elementwise_minimum(mt, ts[3]), ts[4]);
                     mt = __builtin_elementwise_minimum(__builtin_elementwise_minimum(mt, ts[5]), ts[6]);
                     mt = __builtin_elementwise_minimum(mt, ts[7]);
-#ifdef PVM_ABL_Q_RT   // profiling: the candidates found but never queued (counts wrong)
+#ifdef PVV_PROFILE   // ablation bit 128: the candidates found but never queued (counts wrong)
                     if (a.rw[3] == 7778) mt = 3.0e38f;
 #endif
                     if (__builtin_amdgcn_ballot_w64(fj && mt <= G)) {
@@ -2217,9 +2053,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                 static_assert(kMSet == 4, "band selects");
                 auto bsel = [&](int j) -> h4f { return j == 0 ? bf[0] : j == 1 ? bf[1] : j == 2 ? bf[2] : bf[3]; };
                 while (hm0 | hm1) {
-                    int pk[PVM_BANDK], jk[PVM_BANDK], nk = 0;
+                    int pk[kMBandK], jk[kMBandK], nk = 0;
 #pragma unroll
-                    for (int k = 0; k < PVM_BANDK; ++k) {
+                    for (int k = 0; k < kMBandK; ++k) {
                         pk[k] = 0; jk[k] = 0;
                         if (hm0 | hm1) {
                             int bit;
@@ -2230,66 +2066,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                         }
                     }
                     nfix += nk;
-                    h4f ak[PVM_BANDK];
+                    h4f ak[kMBandK];
 #pragma unroll
-                    for (int k = 0; k < PVM_BANDK; ++k) ak[k] = afrag(pk[k]);
-                    f32x16 ck[PVM_BANDK];
+                    for (int k = 0; k < kMBandK; ++k) ak[k] = afrag(pk[k]);
+                    f32x16 ck[kMBandK];
 #pragma unroll
-                    for (int k = 0; k < PVM_BANDK; ++k)
+                    for (int k = 0; k < kMBandK; ++k)
                         ck[k] = __builtin_amdgcn_mfma_f32_32x32x8f16(ak[k], bsel(jk[k]), zero, 0, 0, 0);
 #pragma unroll
-                    for (int k = 0; k < PVM_BANDK; ++k)
+                    for (int k = 0; k < kMBandK; ++k)
                         if (k < nk) band_test(ck[k], pk[k], jk[k]);
                 }
-#else
-                while (hm0 | hm1) {
-                    int bit;
-                    if (hm0) { bit = __builtin_ctzll(hm0); hm0 &= hm0 - 1; }
-                    else { bit = 64 + __builtin_ctzll(hm1); hm1 &= hm1 - 1; }
-                    const int p = bit / kMSet, j = bit % kMSet;
-                    ++nfix;
-                    h4f bj = bf[0];
-#pragma unroll
-                    for (int k = 1; k < kMSet; ++k)
-                        if (j == k) bj = bf[k];
-                    float hxj, hyj, sj, gBj;
-                    hscale(j, hxj, hyj, sj, gBj);
-                    const bool fj = (hfm >> j) & 1u;
-                    const float G = a.gzf * gBj * sj * 1.001f;
-                    const f32x16 c = __builtin_amdgcn_mfma_f32_32x32x8f16(afrag(p), bj, zero, 0, 0, 0);
-                    // register pair (2q, 2q + 1) = rows 2m, 2m + 1 with
-                    // m = (q & 1) + 4 (q >> 1) + 2 half: pixel m of the batch.
-                    // Every pair's test first, one ballot for the lot: most
-                    // flagged MFMAs hold no pair inside its own bound, and
-                    // then the per-pair ballots and queue writes are skipped
-                    uint32_t um = 0;
-                    float zs[8];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const float X = c[2 * q], Y = c[2 * q + 1];
-                        const float zq = X - fabsf(Y);
-                        const float g = fmaf(kx, fabsf(X), fmaf(ky, fabsf(Y), G));
-                        const int pix = p * kMB + (q & 1) + 4 * (q >> 1) + 2 * half;
-                        zs[q] = zq;
-                        um |= (fj && pix < np && fabsf(zq) <= g) ? 1u << q : 0u;
-                    }
-                    if (__builtin_amdgcn_ballot_w64(um != 0)) {
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) {
-                            const bool u = (um >> q) & 1u;
-                            const uint64_t m = __builtin_amdgcn_ballot_w64(u);
-                            if (m) {
-                                const int pix = p * kMB + (q & 1) + 4 * (q >> 1) + 2 * half;
-                                if (nq > kMQueue - kWave) flush();
-                                const int at = nq + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                                if (u) bq[at] = (uint32_t)pix | ((uint32_t)j << 9) | ((uint32_t)col << 11) | ((signbit(zs[q]) ? 0u : 1u) << 16);
-                                nq += __popcll(m);
-                                nqd += __popcll(m);
-                            }
-                        }
-                    }
-                }
-#endif
                 { const uint64_t t = cyc(); c_band += t - c_mark; c_fix += t - c_mark; c_mark = t; }
                 flush();
                 __builtin_amdgcn_wave_barrier();
@@ -2299,9 +2086,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                 for (int j = 0; j < kMSet; ++j) {
                     uint64_t mm = __builtin_amdgcn_ballot_w64(((hxm >> j) & 1u) && half == 0);
                     nxo += __popcll(mm);
-#ifdef PVM_ABL_XO
-                    mm = 0;
-#endif
                     while (mm) {
                         const int l = __builtin_ctzll(mm);
                         mm &= mm - 1;
@@ -3278,12 +3062,7 @@ __device__ __forceinline__ void vote_bytes_seg(const ByteArgs &a, F4 *recs, uint
     uint32_t lof = loff;                                // (loop-carried through the asm below: no copies)
     auto row = [&](const F4 &rec, int i, uint32_t &lo, uint32_t &hi) {
         float nz[kBytePix];
-#ifdef PVVOTE_ABLATE_U1_COMPUTE
-        float m = 3e38f;
-        for (int j = 0; j < kBytePix; ++j) nz[j] = rec.x + (float)j;
-#else
         const float m = zrow(rec, nz);
-#endif
         const uint64_t hit = __builtin_amdgcn_ballot_w64(m <= rec.z);   // flagged rows: rec.z = inf
         lo = pack4(nz[0], nz[1], nz[2], nz[3]);
         hi = pack4(nz[4], nz[5], nz[6], nz[7]);
@@ -3305,9 +3084,6 @@ __device__ __forceinline__ void vote_bytes_seg(const ByteArgs &a, F4 *recs, uint
                 }
             }
         }
-#ifdef PVVOTE_ABLATE_U1_STORE
-        if (lo == 0x12345678u && hi == 0x9abcdef0u) skip = false; else skip = true;
-#endif
         return skip;
     };
     using gbyte = __attribute__((address_space(1))) uint8_t;
@@ -3356,9 +3132,6 @@ __device__ __forceinline__ void vote_bytes_seg(const ByteArgs &a, F4 *recs, uint
     // Exact pass over what is left -- flagged rows, and band rows that found
     // the queue full: the lane's pixels' reference operands are loaded once
     // (one memory round trip), then the reference's sequence decides.
-#ifdef PVVOTE_ABLATE_U1_EXACT
-    dmask = 0;   // profiling ablation only
-#endif
     if (dmask) {
         float2 ec[kBytePix], ed[kBytePix];
 #pragma unroll
@@ -3773,21 +3546,22 @@ uint64_t *g_vote_trace = nullptr;   // trace builds only (pv_debug_set_vote_trac
 
 // Kernel selection and grid shapes are compile-time constants of the build
 // (pvnet_amd/build.py; pv_build_config() reports them): no environment
-// variable changes what the library runs.  The A/B measurements behind each
-// default are in the comments and DESIGN.md section 7.
-#ifndef PVV_ABL
-#define PVV_ABL 0           // profiling ablations only (outputs wrong): 1 no k_compact, 2 no k_hyp_gen, 4 no vote, 8 no refine, 16 no k_fg_count
+// variable changes what the library runs, and the default build has no switch
+// that drops work.  The A/B measurements behind each default are in the
+// comments and DESIGN.md section 7; the variants measured and removed are in
+// DESIGN.md's appendix "Removed variants".
+#ifdef PVV_PROFILE
+// profiling builds only (tools/build_variant.py profile -DPVV_PROFILE): the
+// ablation bits in effect (pv_debug_set_ablation, set between captures by the
+// profiling tools; outputs wrong): 1 no k_compact, 2 no k_hyp_gen, 4 no vote,
+// 8 no refine, 16 no k_fg_count, 32 an empty launch in k_hyp_gen's place,
+// 64 k_vote_mfma's band pairs not re-checked, 128 found but not queued
+int g_abl = 0;
+#else
+constexpr int g_abl = 0;
 #endif
-// the ablation bits in effect (pv_debug_set_ablation; set between captures by profiling tools only)
-int g_abl = PVV_ABL;
 #ifndef PVV_VM_BPC
 #define PVV_VM_BPC 3        // k_vote_mfma blocks per CU (tools/vm_ab.sh, 8 in flight: 4 -> 36.6k images/s, 3 -> 40.2k, 2 -> 39.7k)
-#endif
-#ifndef PVV_HYPGEN
-#define PVV_HYPGEN 1        // hypotheses by k_hyp_gen before the vote: 34.6k -> 36.6k images/s, vote 35.2 -> 31.8 us
-#endif
-#ifndef PVV_HYPFUSE
-#define PVV_HYPFUSE 1       // ... made by k_compact's first blocks instead of a k_hyp_gen launch (round 6)
 #endif
 #ifndef PVV_BYTES_XCD
 #define PVV_BYTES_XCD 1     // k_vote_bytes: XCD-contiguous item ranges (31.1 vs 31.9 us interleaved)
@@ -3796,25 +3570,18 @@ int g_abl = PVV_ABL;
 #define PVV_BYTES_BAL 1     // k_vote_bytes: CU-balanced grid of full + quarter blocks (33.0 -> 31.1 us)
 #endif
 static_assert(PVV_VM_BPC >= 1 && PVV_VM_BPC <= 4, "k_vote_mfma: 1..4 blocks per CU");
-#ifndef PVV_VM_RW3_0
-#define PVV_VM_RW3_0 0      // k_vote_mfma work weights of its three dispatch rounds (0: even shares)
-#define PVV_VM_RW3_1 0
-#define PVV_VM_RW3_2 0
-#endif
 
-// Test hooks (not in pvvote.h, set only by explicit calls between launches,
-// never during a capture): which fused vote/count kernel the pipeline runs
-// (pv_debug_set_vote_kernel: the tests check both in one process) and the
-// byte kernel's band-queue capacity (pv_debug_set_bytes_mode 4: a queue of
-// one entry, so the in-kernel exact pass runs).
-int g_vote_kernel = 0;    // 0: k_vote_mfma (hn a multiple of 512), 1: k_vote_count
-int g_bytes_dbg = 0;
-bool vote_old() { return g_vote_kernel == 1; }
+// Test hooks, not for production (not in pvvote.h, set only by explicit calls
+// between launches, never during a capture): which fused vote/count kernel
+// the pipeline runs (pv_debug_set_vote_kernel: the tests check both in one
+// process) and the byte kernel's band-queue capacity (pv_debug_set_bytes_mode
+// 4: a queue of one entry, so the in-kernel exact pass runs).  Atomic, relaxed:
+// concurrent caller threads read them on every call.
+std::atomic<int> g_vote_kernel{0};   // 0: k_vote_mfma (hn a multiple of 512), 1: k_vote_count
+std::atomic<int> g_bytes_dbg{0};
+bool vote_old() { return g_vote_kernel.load(std::memory_order_relaxed) == 1; }
 // does front_half pre-generate the hypotheses (k_hyp_gen, keypoint-major in w.hypv)?
-bool hyp_pregen_used(int vn, int nh) {
-    (void)vn;
-    return PVV_HYPGEN && ((nh + kGroup - 1) / kGroup) % 4 == 0 && !vote_old();
-}
+bool hyp_pregen_used(int nh) { return ((nh + kGroup - 1) / kGroup) % 4 == 0 && !vote_old(); }
 
 template <bool PREPPED>
 void launch_vote(const VoteArgs &va, int64_t pixel_steps, hipStream_t s) {
@@ -3827,18 +3594,9 @@ void launch_vote(const VoteArgs &va, int64_t pixel_steps, hipStream_t s) {
         VoteArgs vr = va;
         vr.gzf = va.fast ? mfma_gz(va.tau) : 0.f;
         for (int k = 0; k < 4; ++k) vr.rw[k] = 0;
-#ifdef PVM_ABL_FIX_RT
-        vr.rw[3] = 7777;
-#endif
-#ifdef PVM_ABL_Q_RT
-        vr.rw[3] = 7778;
-#endif
-        // a SIMD issues age-first: with one resident block per CU per dispatch
-        // round, the rounds' waves end in start order (tools/vote_trace.py:
-        // 0 / 3.8 / 7.7 us apart with equal shares); weight the rounds' work
-        if (grid == 3 * cu_count() && PVV_VM_RW3_0 > 0) {
-            vr.rw[0] = PVV_VM_RW3_0; vr.rw[1] = PVV_VM_RW3_1; vr.rw[2] = PVV_VM_RW3_2;
-        }
+        // (rw[3]: the sentinels of k_vote_mfma's two band ablations, profiling builds)
+        if (g_abl & 128) vr.rw[3] = 7778;
+        if (g_abl & 64) vr.rw[3] = 7777;
         k_vote_mfma<PREPPED><<<grid, 256, 0, s>>>(vr);
     } else if (va.hgn % 4 == 0) {
         const int grid = vote_grid_steps(pixel_steps, (const void *)k_vote_count<PREPPED, true>, 4);
@@ -3968,7 +3726,7 @@ int front_half(const pv_image_desc *img, const pv_vote_params *prm, int nh, bool
     ca.s = s;
     if ((int64_t)vn * ((nh + kGroup - 1) / kGroup) * P >= (1ll << 31)) return PV_EINVAL;
     // the hypotheses by k_compact's first blocks (compact_hyp) instead of a k_hyp_gen launch
-    const bool hfuse = PVV_HYPFUSE && hyp_pregen_used(vn, nh) && nblk <= kHypMaxChunks && !(g_abl & 2);
+    const bool hfuse = hyp_pregen_used(nh) && nblk <= kHypMaxChunks && !(g_abl & 2);
     ca.hg = HypGen{};
     if (hfuse) {
         ca.hg.nhb = (int)(((int64_t)nh * vn + 255) / 256);
@@ -4000,12 +3758,14 @@ int front_half(const pv_image_desc *img, const pv_vote_params *prm, int nh, bool
     // prologue, overlapped with its first pixel loads) and stores them in
     // the reference layout; by default (hyp_pregen) one k_hyp_gen launch makes
     // them first and the vote kernel (k_vote_mfma) reads them keypoint-major
-    if (hyp_pregen_used(vn, nh)) {
+    if (hyp_pregen_used(nh)) {
         va.hypv_out = w.hypv;
         const int64_t nt = (int64_t)b * nh * vn;
         if (hfuse) {
         } else if (!(g_abl & 2)) k_hyp_gen<<<(unsigned)((nt + 255) / 256), 256, 0, s>>>(va);
+#ifdef PVV_PROFILE
         else if (g_abl & 32) k_abl_empty<<<1, 64, 0, s>>>(0);
+#endif
         if ((r = last())) return r;
         va.hyp = w.hypv; va.hyp_sb = (int64_t)vn * nh; va.hyp_sv = nh; va.hyp_sh = 1;
     }
@@ -4050,14 +3810,18 @@ const char *pv_version(void) { return PV_VERSION; }
 #define PVV_STR2(x) #x
 #define PVV_STR(x) PVV_STR2(x)
 const char *pv_build_config(void) {
-    return "vote=k_vote_mfma(bpc=" PVV_STR(PVV_VM_BPC) ",wpe=" PVM_WPE_STR ",chunk=" PVV_STR(PVM_CHUNK) ",queue=" PVV_STR(PVM_QUEUE) ",band=" PVV_STR(PVM_BANDV) ",rw=" PVV_STR(PVV_VM_RW3_0) "/"
-           PVV_STR(PVV_VM_RW3_1) "/" PVV_STR(PVV_VM_RW3_2) ")"
-           " hypgen=" PVV_STR(PVV_HYPGEN) " hypfuse=" PVV_STR(PVV_HYPFUSE)
+    // (band, rw, hypgen, hypfuse, fg_cpb, compact_skip: switches since fixed, kept
+    // as literals so that bench records stay comparable across rounds)
+    return "vote=k_vote_mfma(bpc=" PVV_STR(PVV_VM_BPC) ",wpe=" PVM_WPE_STR ",chunk=" PVV_STR(PVM_CHUNK) ",queue=" PVV_STR(PVM_QUEUE) ",band=2,rw=0/0/0)"
+           " hypgen=1 hypfuse=1"
            " refine=" PVV_STR(PVV_REFINE_NJ) "x" PVV_STR(PVV_REFINE_T)
-           " fg_cpb=1/" PVV_STR(8) " compact_skip=" PVV_STR(PVV_COMPACT_SKIP)
+           " fg_cpb=1/8 compact_skip=1"
            " bytes=k_vote_bytes(rows=" PVV_STR(PVV_BYTE_HB) ",xcd=" PVV_STR(PVV_BYTES_XCD) ",bal=" PVV_STR(PVV_BYTES_BAL) ")"
 #ifdef PVV_TRACE
            " TRACE"
+#endif
+#ifdef PVV_PROFILE
+           " PROFILE"
 #endif
         ;
 }
@@ -4135,7 +3899,7 @@ int pv_voting_for_hypothesis(const float *direct, const float *coords, const flo
     ba.fast = fc.fast; ba.thr = fc.thr; ba.tau = fc.tau; ba.gzf = fc.gzf; ba.gzr = fc.gzr;
     ba.nwin = (tn + kByteWin - 1) / kByteWin;
     ba.nhg = (hn + kByteHB - 1) / kByteHB;
-    ba.dbg = g_bytes_dbg;
+    ba.dbg = g_bytes_dbg.load(std::memory_order_relaxed);
     const int64_t items = (int64_t)vn * ba.nwin * ba.nhg;
     if (items >= (1ll << 31)) return PV_EINVAL;   // the kernel's 32-bit item index
     // one launch, no scratch: the operands are made where the blocks stage them
@@ -4227,13 +3991,14 @@ int pv_debug_lookback_self(int32_t on) {
     return rc(hipMemcpyToSymbol(HIP_SYMBOL(g_lb_self), &on, sizeof(on)));
 }
 
-// debug only (profiling tools, never during a capture): pipeline kernels left out of the next
-// launches (bits: 1 k_compact, 2 k_hyp_gen, 4 vote, 8 refine, 16 k_fg_count; 32 with 2: an empty
-// kernel in k_hyp_gen's place); outputs are wrong
+#ifdef PVV_PROFILE
+// profiling builds only (never during a capture): work left out of the next
+// launches (g_abl's bits); outputs are wrong
 int pv_debug_set_ablation(int32_t m) {
     g_abl = m;
     return PV_OK;
 }
+#endif
 
 #ifdef PVV_TRACE
 // trace builds only: per-wave timestamps of the next pipeline vote launches
@@ -4244,16 +4009,12 @@ int pv_debug_set_refine_trace(uint64_t *buf) { return (int)hipMemcpyToSymbol(HIP
 // test hook (not in pvvote.h): which fused vote/count kernel the pipeline runs
 // (0 matrix-core k_vote_mfma, 1 VALU k_vote_count); returns the previous
 int pv_debug_set_vote_kernel(int32_t which) {
-    const int prev = g_vote_kernel;
-    g_vote_kernel = which == 1 ? 1 : 0;
-    return prev;
+    return g_vote_kernel.exchange(which == 1 ? 1 : 0, std::memory_order_relaxed);
 }
 // test hook (not in pvvote.h): the byte kernel's band-queue mode (4: one-entry
 // queue, so band rows take the in-kernel exact pass); returns the previous
 int pv_debug_set_bytes_mode(int32_t dbg) {
-    const int prev = g_bytes_dbg;
-    g_bytes_dbg = dbg == 4 ? 4 : 0;
-    return prev;
+    return g_bytes_dbg.exchange(dbg == 4 ? 4 : 0, std::memory_order_relaxed);
 }
 #ifdef PVVOTE_TRACE_U1
 int pv_debug_set_bytes_trace(uint64_t *buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_btrace), &buf, sizeof(buf)); }
@@ -4277,8 +4038,8 @@ int pv_v3_kernel_launches(int32_t b, int32_t H, int32_t W, int32_t vn, int32_t n
     const int64_t per_img = (int64_t)vn * ((n_hyp + kGroup - 1) / kGroup) * P;
     if (per_img >= (1ll << 31)) return 0;
     const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(b, ((1ll << 31) - 1) / per_img));
-    const bool pre = hyp_pregen_used(vn, n_hyp);
-    const bool fuse = PVV_HYPFUSE && pre && nblk <= kHypMaxChunks;
+    const bool pre = hyp_pregen_used(n_hyp);
+    const bool fuse = pre && nblk <= kHypMaxChunks;
     return 2 + (pre && !fuse ? 1 : 0) + (b + chunk - 1) / chunk + 1;
 }
 
@@ -4297,7 +4058,7 @@ int pv_ransac_voting_v3(const pv_image_desc *img, const pv_vote_params *prm, flo
     const int b = img->b, vn = img->vn;
     const int64_t P = (int64_t)img->H * img->W;
     // hypotheses keypoint-major when the pipeline pre-generated them (coalesced), else the reference layout
-    const bool hv = hyp_pregen_used(vn, nh);
+    const bool hv = hyp_pregen_used(nh);
     auto *kref = nh > kRefineLdsHyp ? k_refine_solve<true> : k_refine_solve<false>;
     if (!(g_abl & 8)) kref<<<dim3(kRefineNJ, vn, b), kRT, 0, s>>>(w.counts, hv ? w.hypv : w.hyp, (int64_t)nh * vn,
                                                           hv ? nh : 1, hv ? 1 : vn, w.pex, w.tn, P, vn, nh,

@@ -41,6 +41,28 @@ def test_library_is_built_for_gfx950():
     assert b"gfx950" in blob
 
 
+@pytest.fixture(scope="module")
+def default_cdll(lib):
+    """The default build itself (not a PVVOTE_LIB variant), as a plain ctypes.CDLL."""
+    return ctypes.CDLL(os.path.join(REPO, "pvnet_amd", "libpvvote.so"))
+
+
+def test_build_config_of_default_build(default_cdll):
+    # byte for byte the string bench records carry (profiles/r06/bench_confirm_final.json):
+    # the fields of switches since fixed are literals, so records stay comparable
+    default_cdll.pv_build_config.restype = ctypes.c_char_p
+    assert default_cdll.pv_build_config() == (
+        b"vote=k_vote_mfma(bpc=3,wpe=4,chunk=352,queue=128,band=2,rw=0/0/0) hypgen=1 hypfuse=1 "
+        b"refine=16x256 fg_cpb=1/8 compact_skip=1 bytes=k_vote_bytes(rows=64,xcd=1,bal=1)")
+
+
+def test_default_build_exports_test_hooks_only(default_cdll):
+    # the switch that drops work exists in -DPVV_PROFILE builds only
+    assert not hasattr(default_cdll, "pv_debug_set_ablation")
+    for name in ("pv_debug_set_vote_kernel", "pv_debug_set_bytes_mode", "pv_debug_lookback_self"):
+        assert hasattr(default_cdll, name), name
+
+
 def test_version_and_errors(lib):
     assert lib.pv_version().decode().startswith("pvvote")
     assert lib.pv_error_string(0) == b"ok"

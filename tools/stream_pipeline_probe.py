@@ -16,7 +16,9 @@ pv_debug_set_ablation so that each call keeps only its stage:
 
 with a ring of nws workspaces (front(j) after refine(j - nws)).  Every frame's
 keypoints are checked against its generating keypoints.  The plain 8-lane
-stream runs first for reference."""
+stream runs first for reference.  Needs a profiling build of the library:
+    python tools/build_variant.py profile -DPVV_PROFILE
+    PVVOTE_LIB=variants/profile.so python tools/stream_pipeline_probe.py"""
 import argparse
 import ctypes
 import os
@@ -124,6 +126,9 @@ def pipelined(dev, segs, vers, kps, steps, nf, nv, nr, nws, M=int(os.environ.get
 
 
 def main():
+    if not hasattr(_lib.load(), "pv_debug_set_ablation"):
+        sys.exit("needs a -DPVV_PROFILE build: python tools/build_variant.py profile -DPVV_PROFILE, "
+                 "then PVVOTE_LIB=variants/profile.so")
     steps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
     cfgs = [tuple(int(x) for x in c.split(",")) for c in sys.argv[2:]] or [(2, 4, 2, 16), (4, 4, 4, 16)]
     dev = torch.device("cuda:0")

@@ -9,7 +9,9 @@
 holds a real frame's records, hypotheses and pixel count), then captures the
 graph with the kernels of mask m left out (pv_debug_set_ablation: 1 k_compact,
 2 k_hyp_gen, 4 vote, 8 refine, 16 k_fg_count): what the stream costs without
-them, on real data.
+them, on real data.  `abl` needs a profiling build of the library:
+    python tools/build_variant.py profile -DPVV_PROFILE
+    PVVOTE_LIB=variants/profile.so python tools/stream_timeline.py abl ...
 
 `empty` replays graphs of the headline's shape (1,024 frames per replay, 8
 lanes forked from the capture stream and joined) whose frames are n = 1..5
@@ -82,6 +84,9 @@ def main():
         import ctypes
         from pvnet_amd import _lib
         L = _lib.load()
+        if not hasattr(L, "pv_debug_set_ablation"):
+            sys.exit("abl needs a -DPVV_PROFILE build: python tools/build_variant.py profile -DPVV_PROFILE, "
+                     "then PVVOTE_LIB=variants/profile.so")
         L.pv_debug_set_ablation.argtypes = [ctypes.c_int32]
         segs, vers, kps, tn = bench.make_fields(0, 1, 64, dev)
         orig = bench.new_graph
