@@ -14,9 +14,10 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "csrc", "pvvote.hip")
-SRCS = [SRC, os.path.join(HERE, "csrc", "pvpnp.hip"), os.path.join(HERE, "csrc", "pvdecoder.hip"),
-        os.path.join(HERE, "csrc", "pvconv.hip")]
+CSRC = os.path.join(HERE, "csrc")
+# the translation units (csrc/pvvote.hip's head comment maps the vote library's)
+SRCS = [os.path.join(CSRC, n) for n in (
+    "pvvote.hip", "pvcompact.hip", "pvrefine.hip", "pvevd.hip", "pvpnp.hip", "pvdecoder.hip", "pvconv.hip")]
 HDR = os.path.join(REPO, "include", "pvvote.h")
 OUT = os.path.join(HERE, "libpvvote.so")
 ARCH = os.environ.get("PVVOTE_ARCH", "gfx950")
@@ -49,11 +50,17 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found (ROCm install required to build libpvvote.so)")
 
 
-def needs_build() -> bool:
-    if not os.path.exists(OUT):
+def stale(out: str) -> bool:
+    """Is `out` missing, or older than any source under csrc/, the public header or this file?"""
+    if not os.path.exists(out):
         return True
-    t = os.path.getmtime(OUT)
-    return any(os.path.getmtime(p) > t for p in (*SRCS, HDR, __file__))
+    t = os.path.getmtime(out)
+    deps = [os.path.join(CSRC, n) for n in os.listdir(CSRC) if n.endswith((".hip", ".h"))]
+    return any(os.path.getmtime(p) > t for p in (*deps, HDR, __file__))
+
+
+def needs_build() -> bool:
+    return stale(OUT)
 
 
 def build(force: bool = False, extra=()) -> str:
@@ -67,10 +74,14 @@ def build(force: bool = False, extra=()) -> str:
     return OUT
 
 
-def asm(path: str = os.path.join(HERE, "csrc", "pvvote.gfx950.s")) -> str:
-    """Device assembly for inspection (kernel resource usage, v_cmp/s_bcnt1 loops)."""
-    cmd = [hipcc(), *[f for f in HIPCC_FLAGS if f not in ("-shared", "-fPIC", "-Wall")],
-           "--cuda-device-only", "-S", "-o", path, SRC]
+def asm(tu: str = "pvvote.hip", path: str | None = None, extra=()) -> str:
+    """Device assembly of one translation unit (csrc/TU, or a path) for
+    inspection (kernel resource usage, v_cmp/s_bcnt1 loops); default output
+    csrc/<TU's base name>.gfx950.s."""
+    src = tu if os.path.isabs(tu) else os.path.join(CSRC, tu)
+    path = path or os.path.join(CSRC, os.path.splitext(os.path.basename(src))[0] + ".gfx950.s")
+    cmd = [hipcc(), *[f for f in HIPCC_FLAGS if f not in ("-shared", "-fPIC", "-Wall")], *extra,
+           "--cuda-device-only", "-S", "-o", path, src]
     subprocess.check_call(cmd)
     return path
 

@@ -1,0 +1,69 @@
+// pv_stages.h -- what the stages that have their own translation unit expose
+// to the pipeline (pvvote.hip): each stage's host launcher and its argument
+// struct.  Internal to libpvvote.so (namespace pvv, hidden visibility); the
+// exported C ABI is include/pvvote.h.
+#pragma once
+
+#include "pv_common.h"
+#include "pv_host.h"
+
+namespace pvv __attribute__((visibility("hidden"))) {
+
+#ifdef PVV_PROFILE
+// profiling builds only (tools/build_variant.py profile -DPVV_PROFILE): the
+// ablation bits in effect (pv_debug_set_ablation, set between captures by the
+// profiling tools; outputs wrong): 1 no k_compact, 2 no k_hyp_gen, 4 no vote,
+// 8 no refine, 16 no k_fg_count, 32 an empty launch in k_hyp_gen's place,
+// 64 k_vote_mfma's band pairs not re-checked, 128 found but not queued
+extern int g_abl;
+#else
+constexpr int g_abl = 0;
+#endif
+
+// ---- compaction (pvcompact.hip) -------------------------------------------
+constexpr int kHypMaxChunks = 1536;   // chunks per image the fused hypotheses handle (LDS prefix); more: k_hyp_gen
+struct HypGen {
+    int nhb;                    // hypothesis blocks per image (0: none, k_hyp_gen runs)
+    int nh, vn, min_num, max_num;
+    uint64_t seed;              // the hypotheses' counter RNG (VoteArgs::seed)
+    uint64_t kseed;             // the downsampling keep decisions' (k_compact's seed)
+    const int32_t *idxs;        // [b][nh][vn][2] pixel pairs, or nullptr (counter RNG)
+    const uint8_t *keep;
+    float2 *hyp_out;            // [b][nh][vn]
+    float2 *hypv_out;           // [b][vn][nh]
+    float *diag_hyp;            // [b][nh][vn][2] or nullptr
+    uint64_t *keptbits;         // downsampled images: the compaction blocks' kept ballots [b][nblk][4]
+};
+
+struct CompactArgs {
+    int mask_kind;      // PV_MASK_*
+    bool evd;           // foreground predicate: EVD's `mask == 1` (else `mask.byte() != 0`)
+    MaskView m;
+    VertexView vx;
+    int b, H, W, vn, nblk, min_num, max_num;
+    uint64_t seed;
+    const uint8_t *keep;
+    Workspace ws;
+    HypGen hg;          // hg.nhb > 0: k_compact's first blocks make the hypotheses
+    hipStream_t s;
+};
+
+// k_fg_count + k_compact (+ the fused hypotheses) of one call
+int compact(const CompactArgs &a);
+
+// ---- refine and v5 confidence (pvrefine.hip) ------------------------------
+// k_refine_solve over the workspace's counts; hypv: the hypotheses keypoint-major (w.hypv)
+void launch_refine(const Workspace &w, bool hypv, int b, int vn, int nh, int64_t P, const pv_vote_params *prm,
+                   float *out, const pv_v3_diag &dg, hipStream_t s);
+void launch_point_conf(const Workspace &w, const float *pts, int b, int vn, int64_t P, float thr, float *conf,
+                       hipStream_t s);
+
+// ---- EVD and motion (pvevd.hip) -------------------------------------------
+void launch_evd_with_mean(const Workspace &w, int b, int vn, int nh, int min_num, int min_hyp_num,
+                          const float *mean, float *cov, hipStream_t s);
+void launch_evd_topk(const Workspace &w, int b, int vn, int nh, int min_num, int topk, float *mean, float *cov,
+                     hipStream_t s);
+int launch_motion(int mask_kind, const MaskView &m, const VertexView &vx, int b, int H, int W, int vn, double *acc,
+                  int32_t *cnt, int32_t *ticket, float *out, hipStream_t s);
+
+}  // namespace pvv

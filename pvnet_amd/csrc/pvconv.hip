@@ -39,6 +39,7 @@
 #include <type_traits>
 
 #include "../../include/pvvote.h"
+#include "pv_host.h"
 
 #ifndef PVC_DEC_AHEAD
 #define PVC_DEC_AHEAD 3     // k_dec_conv consumers: fragment reads this many k-steps ahead of their MFMAs
@@ -1291,18 +1292,6 @@ __global__ __launch_bounds__(512) void k_conv64(L1Args a) {
     }
 }
 
-int cu_count_dec() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
 }  // namespace
 
 static int decoder_tail(const void *fm, const void *img, const void *w1, const float *b1, const void *w2,
@@ -1340,11 +1329,10 @@ static int decoder_tail(const void *fm, const void *img, const void *w1, const f
     a.trace = g_tail_trace;
 #endif
     hipStream_t s = (hipStream_t)stream;
-    const int64_t grid = std::min<int64_t>(nt, (int64_t)PVT_WPE * cu_count_dec());   // persistent: PVT_WPE blocks per CU
+    const int64_t grid = std::min<int64_t>(nt, (int64_t)PVT_WPE * pvv::cu_count());   // persistent: PVT_WPE blocks per CU
     if (cout == 20) k_decoder_tail<20><<<(unsigned)grid, 256, 0, s>>>(a);
     else k_decoder_tail<44><<<(unsigned)grid, 256, 0, s>>>(a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PV_OK : (int)e;
+    return pvv::last();
 }
 
 extern "C" int pv_decoder_tail_f16(const void *fm, const void *img, const void *w1, const float *b1, const void *w2,
@@ -1374,7 +1362,7 @@ struct ConvSplit {
 ConvSplit conv_split(int64_t pixels, int32_t cout, int32_t ksteps) {
     const bool wide = cout % kCT == 0;
     const int64_t ntiles = (pixels + kPT - 1) / kPT * (cout / (wide ? kCT : 128));
-    const int cus = cu_count_dec();
+    const int cus = pvv::cu_count();
     const int64_t rem = ntiles % cus;
     int S = rem > 0 ? (int)std::min<int64_t>(4, cus / rem) : 1;
     while (S > 1 && ksteps / S < 4) --S;          // parts of at least 4 K-steps
@@ -1464,8 +1452,7 @@ extern "C" int pv_conv3x3_ex_f16(const void *x, int32_t hin, int32_t win, int32_
     const unsigned grid = (unsigned)(a.nfull + (a.ntiles - a.nfull) * a.nsplit);
     if (wide) k_conv3x3<kCT><<<grid, 64 * kNW, 0, (hipStream_t)stream>>>(a);
     else k_conv3x3<128><<<grid, 64 * kNW, 0, (hipStream_t)stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PV_OK : (int)e;
+    return pvv::last();
 }
 
 extern "C" int pv_conv3x3_f16(const void *x, const void *w, const void *bias, const void *res, const void *rbias,
@@ -1496,10 +1483,9 @@ extern "C" int pv_decoder_conv2s_f16(const void *fm, const void *skip, const voi
     a.rh = (float)(hin - 1) / (float)(a.H - 1);
     a.rw = (float)(win - 1) / (float)(a.W - 1);
     a.slope = slope;
-    const int64_t grid = std::min<int64_t>(nt, cu_count_dec());   // persistent: one block per CU
+    const int64_t grid = std::min<int64_t>(nt, pvv::cu_count());   // persistent: one block per CU
     k_dec_conv<32, 2><<<(unsigned)grid, kDecThreads, 0, (hipStream_t)stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PV_OK : (int)e;
+    return pvv::last();
 }
 
 #ifdef PVC_CLOCK_TRACE
@@ -1533,10 +1519,9 @@ extern "C" int pv_decoder_conv4s_f16(const void *fm, const void *skip, const voi
     a.rh = (float)(hin - 1) / (float)(a.H - 1);
     a.rw = (float)(win - 1) / (float)(a.W - 1);
     a.slope = slope;
-    const int64_t grid = std::min<int64_t>(nt, cu_count_dec());   // persistent: one block per CU
+    const int64_t grid = std::min<int64_t>(nt, pvv::cu_count());   // persistent: one block per CU
     k_dec_conv<64, 4><<<(unsigned)grid, kDecThreads, 0, (hipStream_t)stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PV_OK : (int)e;
+    return pvv::last();
 }
 
 
@@ -1805,10 +1790,9 @@ static int stem_launch(const void *img, const void *w, const void *bias, void *o
     const int64_t nt = (int64_t)n * a.tiles_r * a.tiles_c;
     if (nt >= (1ll << 31)) return PV_EINVAL;
     a.ntiles = (int)nt;
-    const int64_t grid = std::min<int64_t>(nt, cu_count_dec());   // persistent: one block per CU
+    const int64_t grid = std::min<int64_t>(nt, pvv::cu_count());   // persistent: one block per CU
     k_stem<<<(unsigned)grid, 512, 0, (hipStream_t)stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PV_OK : (int)e;
+    return pvv::last();
 }
 
 extern "C" int pv_stem_conv_f16(const void *img, const void *w, const void *bias, void *out, int32_t n, int32_t h,
@@ -1838,8 +1822,7 @@ extern "C" int pv_conv64_f16(const void *x, const void *w, const void *bias, con
     const int64_t nt = (int64_t)n * a.tiles_r * a.tiles_c;
     if (nt >= (1ll << 31)) return PV_EINVAL;
     a.ntiles = (int)nt;
-    const int64_t grid = std::min<int64_t>(nt, cu_count_dec());   // persistent: one block per CU
+    const int64_t grid = std::min<int64_t>(nt, pvv::cu_count());   // persistent: one block per CU
     k_conv64<<<(unsigned)grid, 512, 0, (hipStream_t)stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PV_OK : (int)e;
+    return pvv::last();
 }

@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "../../include/pvvote.h"
+#include "pv_host.h"
 
 namespace {
 
@@ -88,8 +89,7 @@ int up2_cat(const void *x, const void *skip, void *out, int32_t n, int32_t hin, 
     const dim3 grid((unsigned)((wout * (cpad / V) + 255) / 256), (unsigned)(rows < 65535 ? rows : 65535));
     k_up2_cat<T><<<grid, 256, 0, (hipStream_t)stream>>>((const T *)x, (const T *)skip, (T *)out, n, hin, win, c1, c2,
                                                         cpad, rh, rw);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PV_OK : (int)e;
+    return pvv::last();
 }
 
 // --------------------------------------------------------------------------
@@ -161,8 +161,7 @@ int epilogue(const void *x, const void *bias, const void *res, const void *rbias
     k_epilogue<T><<<(unsigned)(blocks < 256 * 64 ? blocks : 256 * 64), 256, 0, (hipStream_t)stream>>>(
         (const T *)x, (const T *)bias, (const T *)res, (const T *)rbias, (const T *)skip, (T *)out, P, c1, c2, act,
         slope);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PV_OK : (int)e;
+    return pvv::last();
 }
 
 // --------------------------------------------------------------------------
@@ -235,8 +234,7 @@ int relu_pool(const void *x, const void *bias, void *x2s, void *pool, int32_t n,
     const int64_t blocks = (total + 255) / 256;
     k_relu_pool<T><<<(unsigned)(blocks < 256 * 64 ? blocks : 256 * 64), 256, 0, (hipStream_t)stream>>>(
         (const T *)x, (const T *)bias, (T *)x2s, (T *)pool, n, h, w, c, ho, wo);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PV_OK : (int)e;
+    return pvv::last();
 }
 
 // --------------------------------------------------------------------------
@@ -362,8 +360,7 @@ int head(const void *x, const float *b1, const float *w2, const float *b2, void 
         k_head<T, 44><<<g, 256, 0, s>>>((const T *)x, b1, w2, b2, (T *)out, P, slope);
     else
         return PV_EINVAL;
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PV_OK : (int)e;
+    return pvv::last();
 }
 
 }  // namespace

@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "../../include/pvvote.h"
+#include "pv_host.h"
 
 namespace {
 
@@ -691,8 +692,7 @@ int pv_uncertainty_pnp(const pv_pnp_batch *batch, double *Rt, const pv_pnp_diag 
     pv_pnp_diag dg{};
     if (diag) dg = *diag;
     k_uncertainty_pnp<<<batch->b, 64, 0, (hipStream_t)stream>>>(*batch, nullptr, Rt, nullptr, dg);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PV_OK : (int)e;
+    return pvv::last();
 }
 
 int pv_uncertainty_pnp_refine(const pv_pnp_batch *batch, const double *init_rt, double *result_rt,
@@ -704,8 +704,7 @@ int pv_uncertainty_pnp_refine(const pv_pnp_batch *batch, const double *init_rt, 
     pv_pnp_diag dg{};
     if (diag) dg = *diag;
     k_uncertainty_pnp<<<batch->b, 64, 0, (hipStream_t)stream>>>(*batch, init_rt, nullptr, result_rt, dg);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PV_OK : (int)e;
+    return pvv::last();
 }
 
 }  // extern "C"

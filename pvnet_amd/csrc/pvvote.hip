@@ -24,19 +24,17 @@
 //     hypothesis, pixels broadcast from LDS).  The byte mask is produced only
 //     by the API entry point voting_for_hypothesis, as coalesced 8-byte
 //     stores (lane = 8 pixels, hypotheses broadcast from LDS).
-#include <hip/hip_fp16.h>
-#include <hip/hip_runtime.h>
-#include <array>
-#include <atomic>
-
-#include <algorithm>
-#include <type_traits>
-#include <math.h>
-#include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "../../include/pvvote.h"
+//
+// Files: this one holds the fused vote/count kernels, the stand-alone API
+// kernels, the pipeline and the C ABI.  The stages before and after the vote
+// have their own translation units, reached through pv_stages.h:
+//   pvcompact.hip  k_fg_count, k_compact (+ the fused hypotheses)
+//   pvrefine.hip   k_refine_solve, k_point_conf (v5 confidence)
+//   pvevd.hip      k_evd_with_mean, k_evd_topk, k_motion_vote
+// Shared headers: pv_tunables.h (every -D default with its measurement),
+// pv_common.h (constants, exact reference arithmetic, RNG, views, workspace,
+// reductions), pv_host.h (rc / last / cu_count).
+#include "pv_stages.h"
 
 #define PV_VERSION "pvvote 0.2 (gfx950)"
 
@@ -48,833 +46,15 @@
 #define PVV_TRACE_ON(a) false
 #endif
 
+#ifdef PVV_PROFILE
+namespace pvv __attribute__((visibility("hidden"))) {
+int g_abl = 0;   // pv_debug_set_ablation (pv_stages.h lists the bits)
+}
+#endif
+
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kCompactChunk = 256;           // pixels per compaction block (one per thread)
-constexpr int kVoteChunk = 256;              // pixels per LDS-staged sub-chunk of the vote waves
-// refine blocks per (image, keypoint); measured with the gathering hand-off
-// (tools/ab_libs.sh, two rounds, stream images/s and sequential latency):
-// 16 -> 53.8-54.0k / 47.7-48.6 us, 32 -> 53.2-53.3k / 47.5-48.2 us; with the
-// round-4 ticket hand-off 8 -> 52.7k / 50.9-51.8 us, 16 -> 53.0k / 50.8-51.2,
-// 32 -> 52.5-52.7k / 51.1-51.6 (the round-4 kernel itself: 52.5-52.7k / 52.1)
-#ifndef PVV_REFINE_NJ
-#define PVV_REFINE_NJ 16
-#endif
-constexpr int kRefineNJ = PVV_REFINE_NJ;
-#ifndef PVV_REFINE_T
-#define PVV_REFINE_T 256
-#endif
-// refine block threads (round 5, 16 blocks per keypoint: 256 -> 53.6-53.9k
-// images/s, 512 -> 52.7-53.6k, 1024 -> 44.5k / 50.5 us; round 4, same threads
-// per keypoint: 8 x 256 43.3-43.8k / 51.9 us, 16 x 128 43.0k / 53.6-53.9 us,
-// 32 x 64 41.6k / 59.5 us)
-constexpr int kRT = PVV_REFINE_T;
-// a refine block's published partial: 5 least-squares sums (fp64) + its winner
-// (ratio, index), each value as one 16-B pair of tagged 8-B granules
-constexpr int kRefineGran = 6;
-constexpr int kRefineLdsHyp = 1024;          // hypotheses per keypoint kept in LDS (more: k_refine_solve<true>)
-// domain of the fast test's error bound
-constexpr float kHypMax = 1.0e17f;           // |hx|,|hy| above -> exact-only hypothesis
-constexpr float kLattice = 2.5e-6f;          // |h - round(h)| below (both axes) -> exact-only
-constexpr float kN1Max = 1.0e18f;            // |direction| above -> exact-only pixel
-
-__host__ __device__ inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-
-// --------------------------------------------------------------------------
-// exact reference arithmetic (contraction is off for the whole file)
-// --------------------------------------------------------------------------
-
-// KU's guards compare a float against the double 1e-6: (double)x < 1e-6 holds
-// exactly when x <= 1e-6f (the float nearest 1e-6 lies below it), so the
-// guard runs in f32 without the two f64 conversions (NaN: false either way)
-__device__ __forceinline__ bool below_1e6(float x) { return x <= 1e-6f; }
-
-// KU:107-125: one (h, v, t) decision.
-__device__ __forceinline__ bool exact_vote(float nx, float ny, float cx, float cy, float hx, float hy,
-                                           float thr) {
-    float dx = hx - cx;
-    float dy = hy - cy;
-    float norm1 = sqrtf(nx * nx + ny * ny);
-    float norm2 = sqrtf(dx * dx + dy * dy);
-    if (below_1e6(norm1) || below_1e6(norm2)) return false;
-    float angle_dist = (dx * nx + dy * ny) / (norm1 * norm2);
-    return angle_dist > thr;
-}
-
-// exact_vote's decision for K6's one hypothesis per keypoint, settled by a
-// squared comparison where that is provably the same (*und: not settled, the
-// exact sequence must decide): on the domain below
-// (squared norms in [1e-11, 1e18]: KU's 1e-6 guards pass, nothing over- or
-// underflows) the exact sequence's angle is dot / (|n| |d|) within 4 roundings
-// (2.4e-7 relative) and dot^2 / (thr^2 |n|^2 |d|^2) is within 5 roundings of
-// its square, so outside a 2e-6 band around equality both decide alike;
-// inside the band, outside the domain, or for thr outside [1e-3, 1] (`fast`
-// false), the exact sequence decides.  `thr2` = thr * thr.
-__device__ __forceinline__ void refine_vote_pre(float nx, float ny, float cx, float cy, float hx, float hy,
-                                                float thr2, bool fast, bool *inl, bool *und) {
-    const float dx = hx - cx, dy = hy - cy;
-    const float nn1 = nx * nx + ny * ny;
-    const float nn2 = dx * dx + dy * dy;
-    const float dot = dx * nx + dy * ny;   // the exact sequence's numerator, bit for bit
-    const bool dom = fast && nn1 >= 1e-11f && nn1 <= 1e18f && nn2 >= 1e-11f && nn2 <= 1e18f;
-    const float l = dot * dot, r = thr2 * nn1 * nn2;
-    const bool pos = dot > 0.f;            // else angle <= 0 < thr (or NaN): outlier
-    const bool in = pos && l > r * (1.f + 2e-6f);
-    const bool out = !pos || l < r * (1.f - 2e-6f);
-    *inl = dom && in;
-    *und = !dom || !(in || out);
-}
-
-// KU:28-48: intersection of the lines through two pixels. false = degenerate.
-__device__ __forceinline__ bool exact_intersect(float dx0, float dy0, float cx0, float cy0, float dx1, float dy1,
-                                                float cx1, float cy1, float *ox, float *oy) {
-    float nx0 = dy0, ny0 = -dx0;
-    float nx1 = dy1, ny1 = -dx1;
-    float d0 = nx1 * ny0 - nx0 * ny1;
-    if (below_1e6(fabsf(d0))) return false;
-    float d1 = ny1 * nx0 - ny0 * nx1;
-    if (below_1e6(fabsf(d1))) return false;
-    float p0 = nx0 * cx0 + ny0 * cy0;
-    float p1 = nx1 * cx1 + ny1 * cy1;
-    *oy = (nx1 * p0 - nx0 * p1) / d0;
-    *ox = (ny1 * p0 - ny0 * p1) / d1;
-    return true;
-}
-
-// Is hypothesis (hx, hy) outside the fast test's domain?  Non-finite, huge, or
-// within 2.5e-6 of an integer lattice point (pixel centres are integers, so
-// only such hypotheses can come within the reference's norm2 < 1e-6 guard).
-__device__ __forceinline__ bool hyp_exact_only(float hx, float hy) {
-    bool big = !(fabsf(hx) <= kHypMax) || !(fabsf(hy) <= kHypMax);   // also NaN/inf
-    bool lat = fabsf(hx - rintf(hx)) < kLattice && fabsf(hy - rintf(hy)) < kLattice;
-    return big || lat;
-}
-
-__device__ __forceinline__ uint64_t ballot(bool x) { return __ballot(x); }
-
-__device__ __forceinline__ int lane_id() { return __lane_id(); }
-
-__device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
-
-// --------------------------------------------------------------------------
-// RNG (counter based; the reference uses torch's device RNG, which cannot be
-// reproduced -- parity tests inject idxs / keep-masks instead)
-// --------------------------------------------------------------------------
-__host__ __device__ inline uint64_t mix64(uint64_t z) {
-    z += 0x9e3779b97f4a7c15ull;
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-
-// 32-bit avalanche (lowbias32 constants); two rounds keyed by the seed
-__host__ __device__ inline uint32_t hash32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du;
-    x ^= x >> 15; x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-__device__ inline int32_t rand_index(uint64_t seed, uint64_t key, int32_t n) {
-    uint32_t r = hash32(hash32((uint32_t)key ^ (uint32_t)seed) + (uint32_t)(key >> 32) + (uint32_t)(seed >> 32));
-    return (int32_t)(((uint64_t)r * (uint32_t)n) >> 32);
-}
-
-__device__ inline float rand_unit(uint64_t seed, uint64_t key) {
-    return (float)(mix64(seed ^ mix64(key ^ 0x5bd1e995ull)) >> 40) * (1.0f / 16777216.0f);
-}
-
-// --------------------------------------------------------------------------
-// masks
-// --------------------------------------------------------------------------
-struct MaskView {
-    const void *p;
-    int64_t s0, s1, s2, s3;
-};
-
-// foreground predicate.  V3: RV:533 `mask.byte()` != 0.  EVD: RV:340 `mask == 1`.
-// SEG: argmax over 2 logits == 1 (torch.argmax: first max wins, NaN is max).
-template <int KIND, bool EVD>
-__device__ __forceinline__ bool is_fg(const MaskView &m, int b, int r, int c) {
-    if constexpr (KIND == PV_MASK_SEG_F32 || KIND == PV_MASK_SEG_F16) {
-        int64_t o = b * m.s0 + r * m.s2 + c * m.s3;
-        float s0, s1;
-        if constexpr (KIND == PV_MASK_SEG_F32) {
-            s0 = ((const float *)m.p)[o];
-            s1 = ((const float *)m.p)[o + m.s1];
-        } else {
-            s0 = __half2float(((const __half *)m.p)[o]);
-            s1 = __half2float(((const __half *)m.p)[o + m.s1]);
-        }
-        if (isnan(s0)) return false;
-        if (isnan(s1)) return true;
-        return s1 > s0;
-    } else {
-        int64_t o = b * m.s0 + r * m.s1 + c * m.s2;
-        int64_t v;
-        if constexpr (KIND == PV_MASK_I64) v = ((const int64_t *)m.p)[o];
-        else if constexpr (KIND == PV_MASK_I32) v = ((const int32_t *)m.p)[o];
-        else v = ((const uint8_t *)m.p)[o];
-        if constexpr (EVD) return v == 1;
-        else return (uint8_t)v != 0;
-    }
-}
-
-// --------------------------------------------------------------------------
-// workspace
-// --------------------------------------------------------------------------
-struct Workspace {
-    int32_t *counts;    // [b][vn][nh]   zeroed by k_fg_count
-    uint4 *refslot;     // [b][vn][kRefineNJ][kRefineGran] zeroed by k_fg_count: k_refine_solve's tagged partials
-    int32_t *dsagg;     // [b][nblk]     zeroed by k_fg_count: downsampled count + 1 per block (look-back)
-    int32_t *confc;     // [b][vn][2]    zeroed by k_fg_count: v5 confidence count, ticket
-    int64_t zero_words; // counts + refslot + dsagg + confc (contiguous)
-    int32_t *tn;        // [b] compacted pixels (0 = image skipped)
-    int32_t *fgtot;     // [b] foreground before downsampling
-    int32_t *blkcnt;    // [b][nblk]
-    int32_t *grpcnt;    // [b][ceil(nblk / kFgWideCPB)]: the wide k_fg_count blocks' sums (large grids only)
-    uint64_t *fgbits;   // [b][nblk][4] foreground ballot of each wave of a k_fg_count block
-    uint64_t *keptbits; // [b][nblk][4] downsampled images: k_compact's kept ballots (for compact_hyp)
-    float4 *pex;        // [b][vn][P]   exact pixel data (cx, cy, nx, ny): reference operands
-    float2 *hyp;        // [b][nh][vn]  (reference layout)
-    float2 *hypv;       // [b][vn][nh]  keypoint-major copy (pre-generated hypotheses)
-    size_t total;
-};
-
-Workspace carve(void *base, int b, int H, int W, int vn, int nh) {
-    Workspace w{};
-    int64_t P = (int64_t)H * W;
-    int64_t nblk = (P + kCompactChunk - 1) / kCompactChunk;
-    char *p = (char *)base;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { char *q = p ? p + off : nullptr; off = align_up(off + bytes, 256); return q; };
-    const int64_t ncnt = align_up((int64_t)b * vn * nh, 4);            // refslot 16-B aligned
-    const int64_t nslot = (int64_t)b * vn * kRefineNJ * kRefineGran;
-    w.zero_words = ncnt + 4 * nslot + b * nblk + 2 * (int64_t)b * vn;
-    w.counts = (int32_t *)take(4 * w.zero_words);
-    w.refslot = w.counts ? (uint4 *)(w.counts + ncnt) : nullptr;
-    w.dsagg = w.counts ? (int32_t *)(w.refslot + nslot) : nullptr;
-    w.confc = w.counts ? w.dsagg + b * nblk : nullptr;
-    w.tn = (int32_t *)take(4 * b);
-    w.fgtot = (int32_t *)take(4 * b);
-    w.blkcnt = (int32_t *)take(4 * b * nblk);
-    w.grpcnt = (int32_t *)take(4 * b * ((nblk + 7) / 8));
-    w.fgbits = (uint64_t *)take(8 * 4 * b * nblk);
-    w.keptbits = (uint64_t *)take(8 * 4 * b * nblk);
-    w.pex = (float4 *)take(16 * b * vn * P);
-    w.hyp = (float2 *)take(8 * (int64_t)b * nh * vn);
-    w.hypv = (float2 *)take(8 * (int64_t)b * nh * vn);
-    w.total = (size_t)off;
-    return w;
-}
-
-// agent-scope (device-wide) relaxed atomics for the in-kernel hand-offs
-template <typename T>
-__device__ __forceinline__ void st_agent(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <typename T>
-__device__ __forceinline__ T ld_agent(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// --------------------------------------------------------------------------
-// block helpers (256 threads = 4 waves)
-// --------------------------------------------------------------------------
-// wave sums (every lane gets the sum): DPP within each 16-lane row, then
-// v_permlane16_swap / v_permlane32_swap across rows -- no ds_bpermute round
-// trips (six serial LDS latencies in the __shfl_xor form)
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, true); }
-__device__ __forceinline__ int wave_sum_i(int x) {
-    x += dpp_i<0xB1>(x);
-    x += dpp_i<0x4E>(x);
-    x += dpp_i<0x141>(x);
-    x += dpp_i<0x140>(x);
-    const auto r16 = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-    x = (int)(r16[0] + r16[1]);
-    const auto r32 = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-    return (int)(r32[0] + r32[1]);
-}
-__device__ __forceinline__ double wave_sum_d(double x) {
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-}
-// sum over each 16-lane row of the wave (every lane of a row gets its row's
-// sum) by DPP moves: xor 1, xor 2, half-row mirror, row mirror -- VALU
-// operations, not the LDS-routed ds_bpermute of __shfl_xor
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double x) {
-    const uint64_t u = __builtin_bit_cast(uint64_t, x);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xF, 0xF, true);
-    return __builtin_bit_cast(double, ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-}
-template <int CTRL>
-__device__ __forceinline__ uint64_t dpp_u64(uint64_t u) {
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xF, 0xF, true);
-    return ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
-}
-__device__ __forceinline__ uint64_t row_max_u64(uint64_t x) {
-    uint64_t o;
-    o = dpp_u64<0xB1>(x); x = o > x ? o : x;
-    o = dpp_u64<0x4E>(x); x = o > x ? o : x;
-    o = dpp_u64<0x141>(x); x = o > x ? o : x;
-    o = dpp_u64<0x140>(x); x = o > x ? o : x;
-    return x;
-}
-__device__ __forceinline__ double row_sum_d(double x) {
-    x += dpp_d<0xB1>(x);    // quad_perm [1,0,3,2]
-    x += dpp_d<0x4E>(x);    // quad_perm [2,3,0,1]
-    x += dpp_d<0x141>(x);   // row_half_mirror: quad q <-> 1-q within each half row
-    x += dpp_d<0x140>(x);   // row_mirror: half rows swapped
-    return x;
-}
-// sum over the block of (x, y); `sh` holds >= 8 ints
-__device__ __forceinline__ int2 block_sum2(int x, int y, int *sh) {
-    x = wave_sum_i(x);
-    y = wave_sum_i(y);
-    __syncthreads();
-    if (lane_id() == 0) { sh[threadIdx.x / 64] = x; sh[4 + threadIdx.x / 64] = y; }
-    __syncthreads();
-    return make_int2(sh[0] + sh[1] + sh[2] + sh[3], sh[4] + sh[5] + sh[6] + sh[7]);
-}
-
-// ==========================================================================
-// K1: foreground count per 256-pixel chunk (one pixel per thread and chunk)
-// and the chunk's four wave ballots (k_compact reads 32 B instead of the mask
-// again); zeroes the pipeline's counters.  A block takes CPB consecutive
-// chunks, their mask loads issued together (clamped to the image, so no
-// branch sits between them).  One chunk per block for grids that fit the
-// chip at once (a one-image call: tools/lat_ab.sh, 1 chunk 52.1-52.4 us
-// sequential latency, 2 chunks 52.8-53.1, 4 chunks 54.3); kFgWideCPB for
-// larger grids, where one-chunk blocks -- one mask round trip each, eight
-// per CU at a time -- left the kernel bound by block turnover (configs[2],
-// 32 frames: 70 us).
-// ==========================================================================
-#ifndef PVV_FG_WIDE_ABOVE
-#define PVV_FG_WIDE_ABOVE 4096
-#endif
-constexpr int kFgWideCPB = 8;
-constexpr int64_t kFgWideAbove = PVV_FG_WIDE_ABOVE;   // blocks of one chunk above which the wide form runs
-template <int KIND, bool EVD, int CPB>
-__global__ __launch_bounds__(256) void k_fg_count(MaskView m, int H, int W, int32_t *blkcnt, uint64_t *fgbits,
-                                                  int32_t *grpcnt, int nblk, int32_t *zero, int64_t zero_words) {
-    static_assert(kCompactChunk == 256, "one pixel per thread");
-    const int b = blockIdx.y, wid = threadIdx.x / 64;
-    const int64_t P = (int64_t)H * W;
-    {   // zero counts + tickets (read only by later kernels of this pipeline)
-        int64_t g = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
-        int64_t G = (int64_t)gridDim.x * gridDim.y * 256;
-        for (int64_t i = g; i < zero_words; i += G) zero[i] = 0;
-    }
-    __shared__ int sh[CPB][4];
-    bool f[CPB];
-#pragma unroll
-    for (int k = 0; k < CPB; ++k) {
-        const int blk = blockIdx.x * CPB + k;
-        const int64_t p = (int64_t)blk * kCompactChunk + threadIdx.x;
-        const uint32_t pc = (uint32_t)min(p, P - 1);   // every load in range: none behind a branch
-        const bool v = is_fg<KIND, EVD>(m, b, (int)(pc / (uint32_t)W), (int)(pc % (uint32_t)W));
-        f[k] = blk < nblk && p < P && v;
-    }
-#pragma unroll
-    for (int k = 0; k < CPB; ++k) {
-        const int blk = blockIdx.x * CPB + k;   // block-uniform
-        if (blk >= nblk) break;
-        const uint64_t bal = ballot(f[k]);
-        if (lane_id() == 0) {
-            fgbits[((int64_t)b * nblk + blk) * 4 + wid] = bal;
-            sh[k][wid] = __popcll(bal);
-        }
-    }
-    __syncthreads();
-    const int blk = blockIdx.x * CPB + (int)threadIdx.x;
-    if (threadIdx.x < CPB && blk < nblk)
-        blkcnt[b * nblk + blk] = sh[threadIdx.x][0] + sh[threadIdx.x][1] + sh[threadIdx.x][2] + sh[threadIdx.x][3];
-    if (CPB > 1 && threadIdx.x == 0) {   // the block's sum: k_compact's image totals read these
-        int g = 0;
-#pragma unroll
-        for (int k = 0; k < CPB; ++k)
-            if (blockIdx.x * CPB + k < nblk) g += sh[k][0] + sh[k][1] + sh[k][2] + sh[k][3];
-        grpcnt[b * gridDim.x + blockIdx.x] = g;
-    }
-}
-
-// foreground total of image b from the per-block counts (every block of K1b/K2 does this)
-__device__ __forceinline__ int2 image_totals(const int32_t *cnt, int nblk, int upto, int *sh) {
-    int all = 0, pre = 0;
-    for (int j = threadIdx.x; j < nblk; j += 256) {
-        int v = cnt[j];
-        all += v;
-        pre += j < upto ? v : 0;
-    }
-    return block_sum2(all, pre, sh);
-}
-
-// ==========================================================================
-// K2: row-major stream compaction (RV:548-552): coords (x=col, y=row) and the
-// per-keypoint raw directions, keypoint-major so the vote waves read them
-// contiguously.  Reads the [b,H,W,vn,2] view through its strides, so the
-// network's NCHW vertex_pred is gathered directly (no permute copy).
-// ==========================================================================
-// debug-only phase stamps (s_memrealtime) of the compaction blocks; see
-// pv_debug_compact_trace
-#ifdef PVV_TRACE
-__device__ uint64_t g_ctrace[4096 * 4];
-__device__ int g_ctrace_on;
-__device__ __forceinline__ void cstamp(int blk, int k) {
-    if (g_ctrace_on && threadIdx.x == 0 && blk < 4096) g_ctrace[blk * 4 + k] = __builtin_amdgcn_s_memrealtime();
-}
-#else
-__device__ __forceinline__ void cstamp(int, int) {}
-#endif
-
-struct VertexView {
-    const void *p;
-    int kind;
-    int64_t s[5];
-    int32_t extent;     // bytes spanned by one image's [h,w,vn,2] view (< 2^31: buffer-load range)
-};
-
-constexpr int kCompactKp = 12;   // keypoints whose vertex loads a compaction thread keeps in flight at once
-constexpr uint64_t kLookbackSpin = 20000;   // s_memrealtime ticks (100 MHz): 200 us
-__device__ int g_lb_self;   // debug (pv_debug_lookback_self): every look-back count worked out by the waiter
-
-// one chunk (256 pixels) of image b: the whole of a k_compact block
-// (block-uniform early returns; sh holds 8 ints, wcnt 4, pos 256 with TASKS)
-template <int KIND, bool EVD, int VK, bool TASKS>
-__device__ __forceinline__ void compact_chunk(const VertexView &vx, int H, int W, int vn, const int32_t *blkcnt,
-                                              const int32_t *grpcnt, const uint64_t *fgbits, int32_t *dsagg,
-                                              int nblk, int min_num, int max_num, uint64_t seed, const uint8_t *keep,
-                                              int32_t *tn, int32_t *fgtot, float4 *pex, const int b, const int blk,
-                                              int *sh, int *wcnt, uint16_t *pos, uint64_t *keptbits) {
-    static_assert(kCompactChunk == 256, "one pixel per thread");
-    const int64_t P = (int64_t)H * W;
-    const int wid = threadIdx.x / 64, lane = lane_id();
-    cstamp(blk, 0);
-    // a block without foreground has nothing to store; only blocks 0 and
-    // nblk - 1 (which write tn / fgtot) run on.  The downsampling look-back
-    // below takes such a predecessor's kept count as 0 from its k_fg_count
-    // count, without waiting for it.
-    if (blk != 0 && blk != nblk - 1 && blkcnt[b * nblk + blk] == 0) return;
-    // one round trip: this wave's foreground ballot (k_fg_count) beside the
-    // image's per-block counts (the total and this block's row-major offset)
-    const uint64_t fw = fgbits[((int64_t)b * nblk + blk) * 4 + wid];
-    int2 tot;
-    if constexpr (TASKS) {
-        // the image's total and this chunk's prefix from the wide k_fg_count
-        // blocks' sums (8 chunks each) and the chunks before it in its group
-        const int ng = (nblk + 7) / 8, g0 = blk / 8;
-        int all = 0, pre = 0;
-        for (int j = threadIdx.x; j < ng; j += 256) {
-            const int v = grpcnt[b * ng + j];
-            all += v;
-            pre += j < g0 ? v : 0;
-        }
-        if (threadIdx.x < 8 && g0 * 8 + (int)threadIdx.x < blk) pre += blkcnt[b * nblk + g0 * 8 + threadIdx.x];
-        tot = block_sum2(all, pre, sh);
-    } else {
-        tot = image_totals(blkcnt + b * nblk, nblk, blk, sh);
-    }
-    cstamp(blk, 1);
-    const int fgb = tot.x;
-    if (fgb < min_num) {
-        if (blk == 0 && threadIdx.x == 0) { tn[b] = 0; fgtot[b] = fgb; }
-        return;
-    }
-    const bool ds = fgb > max_num;
-    int base = tot.y;
-    if (!ds && blk == 0 && threadIdx.x == 0) {
-        tn[b] = fgb;
-        fgtot[b] = fgb;
-    }
-    const uint32_t p = (uint32_t)blk * kCompactChunk + threadIdx.x;   // H, W <= 65535: fits
-    bool f = (fw >> lane) & 1;
-    if (ds && f) f = keep ? keep[b * P + p] != 0 : rand_unit(seed, (uint64_t)b * P + p) < (float)max_num / (float)fgb;
-    const uint64_t bal = ds ? ballot(f) : fw;
-    const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-    if (lane == 0) wcnt[wid] = __popcll(bal);
-    if (ds && keptbits && lane == 0) {
-        // the kept ballots for compact_hyp, stored before this block's
-        // look-back value is published (the barrier below orders them)
-        st_agent(&keptbits[((int64_t)b * nblk + blk) * 4 + wid], bal);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    // this pixel's vertex loads (all keypoints of a group in flight together),
-    // issued before the block's offsets are known: buffer loads through a
-    // per-image descriptor, one VGPR offset for the pixel and the keypoint /
-    // component plane offsets in SGPRs (host check: the image's view spans
-    // < 2 GiB)
-    const int r = (int)(p / (uint32_t)W), c = (int)(p - (uint32_t)r * W);
-    constexpr int ES = VK == PV_VERTEX_F32 ? 4 : 2;
-    const __amdgpu_buffer_rsrc_t vr = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)((const char *)vx.p + (int64_t)b * vx.s[0] * ES), (short)0, vx.extent, 0x00020000);
-    const int voff = (int)((r * vx.s[1] + c * vx.s[2]) * ES);
-    float nx[kCompactKp], ny[kCompactKp];
-    auto load_group = [&](int v0) {
-#pragma unroll
-        for (int u = 0; u < kCompactKp; ++u) {
-            nx[u] = ny[u] = 0.f;
-            if (f && v0 + u < vn) {
-                const int so = uniform((int)((v0 + u) * vx.s[3] * ES));
-                const int s4 = uniform((int)(vx.s[4] * ES));
-                if constexpr (VK == PV_VERTEX_F32) {
-                    nx[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(vr, voff, so, 0));
-                    ny[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(vr, voff, so + s4, 0));
-                } else {
-                    nx[u] = __half2float(__ushort_as_half(__builtin_amdgcn_raw_buffer_load_b16(vr, voff, so, 0)));
-                    ny[u] = __half2float(__ushort_as_half(__builtin_amdgcn_raw_buffer_load_b16(vr, voff, so + s4, 0)));
-                }
-            }
-        }
-    };
-    if constexpr (!TASKS) load_group(0);
-    __syncthreads();
-    const int nsel = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-    int off = below;
-    for (int q = 0; q < wid; ++q) off += wcnt[q];
-    if constexpr (TASKS) {
-        if (f) pos[off] = (uint16_t)threadIdx.x;   // the block's selected pixels in rank order
-    }
-    if (ds) {
-        // Downsampled offsets by look-back: publish this block's kept count
-        // (+1, so 0 = not yet; k_fg_count zeroed the array), then add up the
-        // earlier blocks' counts, waiting for each.  No dispatch order is
-        // assumed: a count not seen within kLookbackSpin (a block not yet
-        // scheduled) is worked out by the waiting thread itself from the
-        // foreground ballots and the keep decisions, so every wait ends.
-        int32_t *agg = dsagg + (int64_t)b * nblk;
-        if (threadIdx.x == 0) {
-            st_agent(&agg[blk], nsel + 1);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        const bool self_all = g_lb_self != 0;
-        int pre = 0;
-        // one deadline per thread (not per predecessor): after kLookbackSpin
-        // the thread stops waiting and counts every unseen predecessor itself,
-        // so no thread waits longer than kLookbackSpin in all
-        const uint64_t t_dead = __builtin_amdgcn_s_memrealtime() + kLookbackSpin;
-        for (int j = threadIdx.x; j < blk; j += 256) {
-            if (blkcnt[b * nblk + j] == 0) continue;   // no foreground: kept 0 (the block may not publish)
-            int v = self_all ? 0 : ld_agent(&agg[j]);
-            if (v == 0 && !self_all)
-                while ((v = ld_agent(&agg[j])) == 0 && __builtin_amdgcn_s_memrealtime() < t_dead)
-                    __builtin_amdgcn_s_sleep(1);
-            if (v == 0) {   // block j's kept count from its ballots
-                for (int q = 0; q < 4; ++q) {
-                    uint64_t w = fgbits[((int64_t)b * nblk + j) * 4 + q];
-                    while (w) {
-                        const uint32_t pj = (uint32_t)j * kCompactChunk + q * 64 + __builtin_ctzll(w);
-                        w &= w - 1;
-                        v += keep ? keep[b * P + pj] != 0
-                                  : rand_unit(seed, (uint64_t)b * P + pj) < (float)max_num / (float)fgb;
-                    }
-                }
-                ++v;
-            }
-            pre += v - 1;
-        }
-        base = block_sum2(pre, 0, sh).x;
-        if (blk == nblk - 1 && threadIdx.x == 0) { tn[b] = base + nsel; fgtot[b] = fgb; }
-    }
-    cstamp(blk, 2);
-    // the selected pixel's records at t = base + its rank: consecutive
-    // selected pixels write consecutive records of each keypoint
-    float4 *eb = pex + (int64_t)b * vn * P;
-    if constexpr (TASKS) {
-        // one (selected pixel, keypoint) record per thread and pass, keypoint
-        // major: the block's nsel x vn records spread over all its lanes (with
-        // a sparse mask a lane-per-pixel store pass runs ~8 % of its lanes)
-        __syncthreads();   // pos written
-        const int n = nsel * vn;
-        const int s4 = uniform((int)(vx.s[4] * ES));
-        for (int i = (int)threadIdx.x; i < n; i += 256) {
-            const int v = (int)((uint32_t)i / (uint32_t)nsel), k = i - v * nsel;
-            const uint32_t pp = (uint32_t)blk * kCompactChunk + pos[k];
-            const int rr = (int)(pp / (uint32_t)W), cc = (int)(pp - (uint32_t)rr * W);
-            const int vo = (int)((rr * vx.s[1] + cc * vx.s[2] + v * vx.s[3]) * ES);
-            float x, y;
-            if constexpr (VK == PV_VERTEX_F32) {
-                x = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(vr, vo, 0, 0));
-                y = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(vr, vo, s4, 0));
-            } else {
-                x = __half2float(__ushort_as_half(__builtin_amdgcn_raw_buffer_load_b16(vr, vo, 0, 0)));
-                y = __half2float(__ushort_as_half(__builtin_amdgcn_raw_buffer_load_b16(vr, vo, s4, 0)));
-            }
-            const int64_t t = base + k;   // (bounded as below)
-            if (t < P) eb[(int64_t)v * P + t] = make_float4((float)cc, (float)rr, x, y);
-        }
-        cstamp(blk, 3);
-        return;
-    }
-    const int64_t t = base + off;
-    // t < fg <= P whenever the counts are this call's own; the bound keeps a
-    // workspace shared by two calls in flight (a caller error) from writing
-    // past the image's records
-    const bool store = f && t < P;
-    for (int v0 = 0; v0 < vn; v0 += kCompactKp) {
-        if (v0 > 0) load_group(v0);
-        if (store) {
-#pragma unroll
-            for (int u = 0; u < kCompactKp; ++u) {
-                if (v0 + u >= vn) break;
-                const int64_t o = (int64_t)(v0 + u) * P + t;
-                // the reference's operands only: the vote kernel makes the fast
-                // test's (prep_compacted) while it stages them
-                eb[o] = make_float4((float)c, (float)r, nx[u], ny[u]);
-            }
-        }
-    }
-    cstamp(blk, 3);
-}
-
-// ==========================================================================
-// K3 inside K2 (round 6): the hypotheses (KU:11-49, RV:553-557) made by the
-// first `nhb` blocks of k_compact's grid, beside the compaction, instead of a
-// k_hyp_gen launch after it.  Everything they need is k_fg_count's (the
-// kernel before): the image's chunk counts give tn and a chunk prefix (LDS),
-// a pair index t finds its chunk by binary search and its pixel by a bit
-// select in that chunk's four wave ballots, and the pixel's direction is read
-// from the input view -- the same (col, row, nx, ny) k_compact stores as its
-// record, so the hypotheses are bit-identical to k_hyp_gen's.  Downsampled
-// images (fg > max_num) rank the kept pixels: kept counts from the
-// compaction blocks' look-back values (a count not seen within kLookbackSpin
-// is worked out from the ballots and keep decisions), kept bits by the same
-// keep decision.  One dependent trip more than a compaction block (the
-// ballots), one kernel fewer in the call's chain: a k_hyp_gen launch costs
-// the batch-1 stream ~9 % (profiles/r06/ablation.txt).
-// ==========================================================================
-constexpr int kHypMaxChunks = 1536;   // chunks per image the fused hypotheses handle (LDS prefix); more: k_hyp_gen
-struct HypGen {
-    int nhb;                    // hypothesis blocks per image (0: none, k_hyp_gen runs)
-    int nh, vn, min_num, max_num;
-    uint64_t seed;              // the hypotheses' counter RNG (VoteArgs::seed)
-    uint64_t kseed;             // the downsampling keep decisions' (k_compact's seed)
-    const int32_t *idxs;        // [b][nh][vn][2] pixel pairs, or nullptr (counter RNG)
-    const uint8_t *keep;
-    float2 *hyp_out;            // [b][nh][vn]
-    float2 *hypv_out;           // [b][vn][nh]
-    float *diag_hyp;            // [b][nh][vn][2] or nullptr
-    uint64_t *keptbits;         // downsampled images: the compaction blocks' kept ballots [b][nblk][4]
-};
-
-template <int VK>
-__device__ __forceinline__ void read_dir(const __amdgpu_buffer_rsrc_t &vr, int voff, int s4, float &x, float &y) {
-    if constexpr (VK == PV_VERTEX_F32) {
-        x = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(vr, voff, 0, 0));
-        y = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(vr, voff, s4, 0));
-    } else {
-        x = __half2float(__ushort_as_half(__builtin_amdgcn_raw_buffer_load_b16(vr, voff, 0, 0)));
-        y = __half2float(__ushort_as_half(__builtin_amdgcn_raw_buffer_load_b16(vr, voff, s4, 0)));
-    }
-}
-
-// the q-th set bit (0-based) of the 256-bit mask w[0..3]; q < popcount
-__device__ __forceinline__ int select_bit(const uint64_t (&w)[4], int q) {
-    int base = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int c = __popcll(w[k]);
-        if (q < c) {
-            uint64_t x = w[k];
-            uint32_t lo = (uint32_t)x;
-            int off = 0;
-            if (q >= __popc(lo)) { q -= __popc(lo); lo = (uint32_t)(x >> 32); off = 32; }
-            // binary descent on the 32-bit half
-            int pos = 0;
-#pragma unroll
-            for (int sh = 16; sh >= 1; sh >>= 1) {
-                const int c2 = __popc(lo & ((1u << sh) - 1u));
-                if (q >= c2) { q -= c2; lo >>= sh; pos += sh; }
-            }
-            return base + off + pos;
-        }
-        q -= c;
-        base += 64;
-    }
-    return 255;
-}
-
-template <int KIND, bool EVD, int VK>
-__device__ void compact_hyp(const VertexView &vx, int H, int W, int nblk, const int32_t *blkcnt,
-                            const uint64_t *fgbits, const int32_t *dsagg, int32_t *pre, int *sh, const HypGen &g,
-                            int b, int hb) {
-    const int64_t P = (int64_t)H * W;
-    const int per = (nblk + 255) / 256;            // consecutive chunks per thread (<= 6)
-    // ---- the image's chunk counts and their exclusive prefix (one trip)
-    int c[6];
-    const int j0 = (int)threadIdx.x * per;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) c[k] = k < per && j0 + k < nblk ? blkcnt[b * nblk + j0 + k] : 0;
-    auto scan = [&](int (&v)[6]) -> int {        // block exclusive scan into pre[], returns the total
-        int run = 0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) run += v[k];
-        // inclusive wave scan of run (row shifts + row broadcasts)
-        int x = run;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(x, o);
-            if (lane_id() >= o) x += y;
-        }
-        __syncthreads();
-        if (lane_id() == 63) sh[threadIdx.x / 64] = x;
-        __syncthreads();
-        int wpre = 0;
-        for (int w = 0; w < (int)threadIdx.x / 64; ++w) wpre += sh[w];
-        const int total = sh[0] + sh[1] + sh[2] + sh[3];
-        int e = wpre + x - run;
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            if (k < per && j0 + k < nblk) { pre[j0 + k] = e; e += v[k]; }
-        if (threadIdx.x == 0) pre[nblk] = total;
-        __syncthreads();
-        return total;
-    };
-    const int fgb = scan(c);
-    if (fgb < g.min_num) return;                   // tn = 0: no hypotheses (as k_hyp_gen)
-    const bool ds = fgb > g.max_num;
-    const float pk = (float)g.max_num / (float)fgb;
-    auto kept = [&](int64_t p) -> bool {
-        return g.keep ? g.keep[b * P + p] != 0 : rand_unit(g.kseed, (uint64_t)b * P + p) < pk;
-    };
-    int n = fgb;
-    uint32_t seen = 0;                             // ds: chunks whose kept count (and ballots) were published
-    if (ds) {
-        // kept counts from the compaction blocks' look-back values (count + 1)
-        const uint64_t t_dead = __builtin_amdgcn_s_memrealtime() + kLookbackSpin;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            const int j = j0 + k;
-            if (!(k < per && j < nblk) || c[k] == 0) { c[k] = 0; continue; }
-            int v = g_lb_self ? 0 : ld_agent(&dsagg[b * nblk + j]);
-            while (v == 0 && !g_lb_self && __builtin_amdgcn_s_memrealtime() < t_dead) {
-                __builtin_amdgcn_s_sleep(1);
-                v = ld_agent(&dsagg[b * nblk + j]);
-            }
-            if (v != 0) seen |= 1u << k;
-            if (v == 0) {                          // worked out from the ballots and keep decisions
-                for (int q = 0; q < 4; ++q) {
-                    uint64_t w = fgbits[((int64_t)b * nblk + j) * 4 + q];
-                    while (w) {
-                        v += kept((int64_t)j * kCompactChunk + q * 64 + __builtin_ctzll(w));
-                        w &= w - 1;
-                    }
-                }
-                ++v;
-            }
-            c[k] = v - 1;
-        }
-        n = scan(c);
-        // which chunks' kept ballots are published: bit j of the LDS words
-        // after pre[] (pre[nblk + 1 ...]); the rest are worked out below
-        int32_t *pub = pre + nblk + 1;
-        for (int q = (int)threadIdx.x; q < (nblk + 31) / 32; q += 256) pub[q] = 0;
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            if ((seen >> k) & 1u) atomicOr(&pub[(j0 + k) >> 5], 1 << ((j0 + k) & 31));
-        __syncthreads();
-    }
-    n = min(n, (int)P);
-    if (n <= 0) return;
-    // ---- this thread's hypothesis: item i = (h, v) of image b
-    const int i = hb * 256 + (int)threadIdx.x;
-    if (i >= g.nh * g.vn) return;
-    const int h = i / g.vn, v = i - h * g.vn;
-    const int64_t gid = ((int64_t)b * g.nh + h) * g.vn + v;
-    int t[2];
-    if (g.idxs) {
-        t[0] = min(max(g.idxs[gid * 2], 0), n - 1);
-        t[1] = min(max(g.idxs[gid * 2 + 1], 0), n - 1);
-    } else {
-        const uint64_t key = (uint64_t)gid;
-        t[0] = rand_index(g.seed, key * 2, n);
-        t[1] = rand_index(g.seed, key * 2 + 1, n);
-    }
-    int jj[2], rr[2];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {                  // the last chunk with pre <= t (never an empty one)
-        int lo = 0, hi = nblk - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (pre[mid] <= t[e]) lo = mid; else hi = mid - 1;
-        }
-        jj[e] = lo;
-        rr[e] = t[e] - pre[lo];
-    }
-    uint64_t w0[4], w1[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        w0[q] = fgbits[((int64_t)b * nblk + jj[0]) * 4 + q];
-        w1[q] = fgbits[((int64_t)b * nblk + jj[1]) * 4 + q];
-    }
-    if (ds) {                                      // keep only the kept pixels' bits
-        const int32_t *pub = pre + nblk + 1;
-        const bool p0 = g.keptbits && ((pub[jj[0] >> 5] >> (jj[0] & 31)) & 1);
-        const bool p1 = g.keptbits && ((pub[jj[1] >> 5] >> (jj[1] & 31)) & 1);
-        // published: the compaction block's own kept ballots (one load)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (p0) w0[q] = ld_agent(&g.keptbits[((int64_t)b * nblk + jj[0]) * 4 + q]);
-            if (p1) w1[q] = ld_agent(&g.keptbits[((int64_t)b * nblk + jj[1]) * 4 + q]);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (p0 && p1) break;
-            uint64_t m0 = w0[q], m1 = w1[q], x0 = p0 ? 0 : w0[q], x1 = p1 ? 0 : w1[q];
-            if (!p0) m0 = 0;
-            if (!p1) m1 = 0;
-            while (x0) { const int z = __builtin_ctzll(x0); x0 &= x0 - 1;
-                         if (kept((int64_t)jj[0] * kCompactChunk + q * 64 + z)) m0 |= 1ull << z; }
-            while (x1) { const int z = __builtin_ctzll(x1); x1 &= x1 - 1;
-                         if (kept((int64_t)jj[1] * kCompactChunk + q * 64 + z)) m1 |= 1ull << z; }
-            w0[q] = m0; w1[q] = m1;
-        }
-    }
-    constexpr int ES = VK == PV_VERTEX_F32 ? 4 : 2;
-    const __amdgpu_buffer_rsrc_t vr = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)((const char *)vx.p + (int64_t)b * vx.s[0] * ES), (short)0, vx.extent, 0x00020000);
-    const int s4 = (int)(vx.s[4] * ES);
-    float cx[2], cy[2], nx[2], ny[2];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        const int q = select_bit(e == 0 ? w0 : w1, rr[e]);
-        const uint32_t p = (uint32_t)jj[e] * kCompactChunk + (uint32_t)q;
-        const int r = (int)(p / (uint32_t)W), col = (int)(p - (uint32_t)r * W);
-        cx[e] = (float)col;
-        cy[e] = (float)r;
-        read_dir<VK>(vr, (int)((r * vx.s[1] + col * vx.s[2] + v * vx.s[3]) * ES), s4, nx[e], ny[e]);
-    }
-    float x = 0.f, y = 0.f, ox, oy;
-    if (exact_intersect(nx[0], ny[0], cx[0], cy[0], nx[1], ny[1], cx[1], cy[1], &ox, &oy)) { x = ox; y = oy; }
-    g.hyp_out[gid] = make_float2(x, y);
-    if (g.diag_hyp) { g.diag_hyp[gid * 2] = x; g.diag_hyp[gid * 2 + 1] = y; }
-    g.hypv_out[((int64_t)b * g.vn + v) * g.nh + h] = make_float2(x, y);
-}
-
-// TASKS (grids above kFgWideAbove blocks, i.e. batches): the records are
-// written by (pixel, keypoint) tasks spread over the block instead of by the
-// pixel's own lane (configs[2]'s 32 network frames, ~8 % foreground: 69 us).
-// With g.nhb > 0 the grid's first g.nhb blocks per image make the hypotheses.
-template <int KIND, bool EVD, int VK, bool TASKS>
-__global__ __launch_bounds__(256) void k_compact(MaskView, VertexView vx, int H, int W, int vn,
-                                                 const int32_t *blkcnt, const int32_t *grpcnt,
-                                                 const uint64_t *fgbits, int32_t *dsagg,
-                                                 int nblk, int min_num, int max_num, uint64_t seed,
-                                                 const uint8_t *keep, int32_t *tn, int32_t *fgtot, float4 *pex,
-                                                 HypGen g) {
-    __shared__ int sh[8];
-    __shared__ int wcnt[4];
-    __shared__ uint16_t pos[TASKS ? kCompactChunk : 1];
-    __shared__ int32_t pre[kHypMaxChunks + 1 + (kHypMaxChunks + 31) / 32];
-    if ((int)blockIdx.x < g.nhb) {
-        compact_hyp<KIND, EVD, VK>(vx, H, W, nblk, blkcnt, fgbits, dsagg, pre, sh, g, (int)blockIdx.y, (int)blockIdx.x);
-        return;
-    }
-    compact_chunk<KIND, EVD, VK, TASKS>(vx, H, W, vn, blkcnt, grpcnt, fgbits, dsagg, nblk, min_num, max_num, seed, keep, tn,
-                                        fgtot, pex, (int)blockIdx.y, (int)blockIdx.x - g.nhb, sh, wcnt, pos,
-                                        g.nhb > 0 ? g.keptbits : nullptr);
-}
+using namespace pvv;
 
 // ==========================================================================
 // K4: hypotheses (KU:11-49) + fused vote/count.
@@ -1014,28 +194,6 @@ __device__ __forceinline__ float bcast(float x, int lane) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), lane));
 }
 
-// Wave-wide min / max (result in every lane), all on the VALU: DPP within
-// each row of 16 lanes (quad xor 1, quad xor 2, half-row mirror, row
-// mirror), then v_permlane16_swap and v_permlane32_swap across the rows
-// (no LDS round trips, unlike ds_swizzle / ds_bpermute).
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, false));
-}
-template <bool MAX>
-__device__ __forceinline__ float wave_reduce(float x) {
-    auto op = [](float a, float b) { return MAX ? fmaxf(a, b) : fminf(a, b); };
-    x = op(x, dpp_f<0xB1>(x));    // quad_perm [1,0,3,2]
-    x = op(x, dpp_f<0x4E>(x));    // quad_perm [2,3,0,1]
-    x = op(x, dpp_f<0x141>(x));   // row_half_mirror
-    x = op(x, dpp_f<0x140>(x));   // row_mirror
-    const auto r16 = __builtin_amdgcn_permlane16_swap(__float_as_int(x), __float_as_int(x), false, false);
-    x = op(__int_as_float(r16[0]), __int_as_float(r16[1]));
-    const auto r32 = __builtin_amdgcn_permlane32_swap(__float_as_int(x), __float_as_int(x), false, false);
-    return op(__int_as_float(r32[0]), __int_as_float(r32[1]));
-}
-__device__ __forceinline__ float wave_min(float x) { return wave_reduce<false>(x); }
-__device__ __forceinline__ float wave_max(float x) { return wave_reduce<true>(x); }
 
 // fast data of one pixel from its raw direction (API path without a prepped array)
 __device__ __forceinline__ float4 prep_pixel(float cx, float cy, float nx, float ny) {
@@ -1634,15 +792,7 @@ typedef _Float16 h4f __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kMB = 16;                        // pixels per MFMA batch (32 rows: 16 pixels x (X, Y))
-#ifndef PVM_CHUNK
-#define PVM_CHUNK 352
-#endif
-#ifndef PVM_QUEUE
-#define PVM_QUEUE 128
-#endif
-// pixels per sub-chunk: a unit's range (~350 px at configs[1]) in one; 352
-// (with a 128-entry band queue) keeps the block's LDS under 40 KiB, so a
-// fourth block -- the next image's -- fits beside a launch's three per CU
+// pixels per sub-chunk and band pairs queued per wave: pv_tunables.h
 constexpr int kMChunk = PVM_CHUNK;
 constexpr int kMSlots = (kMChunk + 255) / 256; // pixels per thread in the block's staging (2)
 constexpr int kMBatch = kMChunk / kMB;         // batches per sub-chunk (24)
@@ -1675,18 +825,6 @@ __device__ __forceinline__ uint4 form_row(float ax, float ay, float b) {
     return make_uint4(pack_h2(axh, axh), pack_h2(axl, ayh), pack_h2(ayh, ayl), pack_h2(bh, bl));
 }
 
-#ifndef PVM_WPE
-// waves per SIMD the registers are sized for.  Round 2: 3 (152 VGPRs; 4 then
-// spilled across the hot loop): 40.4k -> 41.5k images/s.  Round 6: the kernel
-// needs 129 at 3 -- one over the 128 that lets a fourth wave, the next
-// frame's block, share the SIMD -- and fits 122 without spills at 4: the
-// batch-1 stream 53.2-53.5k -> 54.2-54.6k images/s, latency unchanged
-// (profiles/r06/vote_wpe_ab.txt)
-#define PVM_WPE 4
-#endif
-#define PVM_WPE_STR2(x) #x
-#define PVM_WPE_STR3(x) PVM_WPE_STR2(x)
-#define PVM_WPE_STR PVM_WPE_STR3(PVM_WPE)
 template <bool PREPPED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PVM_WPE))) void k_vote_mfma(VoteArgs a) {
     const int lane = lane_id();
@@ -2159,572 +1297,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
     }
 }
 
-// f32 2x2 inverse as LAPACK sgesv(A, I) (partial pivoting); false if a pivot is 0.
-__device__ inline bool lu2_inv(float a00, float a01, float a10, float a11, float inv[4]) {
-    bool sw = fabsf(a10) > fabsf(a00);
-    if (sw) { float t0 = a00, t1 = a01; a00 = a10; a01 = a11; a10 = t0; a11 = t1; }
-    if (a00 == 0.f) return false;
-    float l = a10 / a00;
-    float u11 = a11 - l * a01;
-    if (u11 == 0.f) return false;
-    for (int jc = 0; jc < 2; ++jc) {
-        float e0 = (jc == 0) ? 1.f : 0.f, e1 = (jc == 1) ? 1.f : 0.f;
-        float b0 = sw ? e1 : e0, b1 = sw ? e0 : e1;
-        float y1 = b1 - l * b0;
-        float x1 = y1 / u11;
-        float x0 = (b0 - a01 * x1) / a00;
-        inv[0 * 2 + jc] = x0;
-        inv[1 * 2 + jc] = x1;
-    }
-    return true;
-}
-
-
-// ==========================================================================
-// K6: winner per (image, keypoint) (RV:567-575) + least-squares partial sums
-// over the winner's inliers (RV:584-599, fp64), kRefineNJ blocks per
-// keypoint; the last block of each image gathers its image's partials, sums
-// them per keypoint in a fixed order, solves (pts = b_inv(ATA) @ ATb, RV:600)
-// with b_inv's batch-wide identity fallback (RV:503-518).
-// Hand-off (cdna_hip_programming.md Guideline 16, R2: the data is the flag):
-// every value travels as 8-B granules {32-bit half, tag}, a pair per 16-B
-// sc1 store; the gathering block re-reads them with 16-B sc1 loads until
-// every tag is set.  The granules are zeroed by k_fg_count every call; no
-// ticket, no drain before a signal, one memory trip from publish to use.
-// ==========================================================================
-#ifdef PVV_TRACE
-__device__ uint64_t *g_refine_trace;   // trace builds only: per-block phase stamps of k_refine_solve
-#define PVR_STAMP(k)                                                                                      \
-    if (g_refine_trace && threadIdx.x == 0)                                                               \
-        g_refine_trace[(((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8 + (k)] = \
-            __builtin_amdgcn_s_memrealtime()
-#else
-#define PVR_STAMP(k)
-#endif
-constexpr uint32_t kRefineTag = 1u;           // granule tag (slots zeroed every call)
-constexpr uint32_t kRefineSpinMax = 1u << 21;  // gather polls before giving up (~seconds): outputs NaN
-// BIG: nh > 1024 hypotheses (the winner's is fetched, not kept in LDS; the
-// counts beyond the first 1024 read in a loop) -- its own instantiation, so
-// the common one has no loop whose loads would make the compiler drain every
-// load in flight before the argmax
-template <bool BIG>
-__global__ __launch_bounds__(kRT) void k_refine_solve(const int32_t *counts, const float2 *hyp, int64_t hsb, int hsv,
-                                                      int hsh, const float4 *pex, const int32_t *tn, int64_t P, int vn,
-                                                      int nh, float thr, uint4 *slot, float confidence, int max_iter,
-                                                      float *out, pv_v3_diag diag) {
-    const int j = blockIdx.x, v = blockIdx.y, b = blockIdx.z;
-    PVR_STAMP(0);
-    __shared__ uint64_t skey[kRT / 16];
-    __shared__ double sacc[kRT / 16][5];   // row sums (16-lane rows)
-    constexpr int HC = kRefineLdsHyp / kRT;         // counts / hypotheses per thread, in registers
-    static_assert(kRefineLdsHyp % kRT == 0, "PVV_REFINE_T divides the LDS hypothesis capacity");
-    __shared__ float2 shyp[kRefineLdsHyp];
-    // Loads are issued in the order they are needed and return in that order:
-    // the pixel count, the keypoint's vote counts and hypotheses (the argmax
-    // needs only those), then this block's pixels (the winner's votes).
-    const int n = min(max(tn[b], 0), (int)P);   // clamped like tn_at: loads stay inside the P records
-    const int32_t *cnt = counts + ((int64_t)b * vn + v) * nh;
-    const float2 *hb = hyp + b * hsb + (int64_t)v * hsv;
-    constexpr bool lds_hyp = !BIG;
-    int32_t c[HC];
-    float2 hh[HC];
-    // (every load unconditional, its index clamped into range, so that no
-    // branch makes the compiler wait for all of them before the first use)
-#pragma unroll
-    for (int q = 0; q < HC; ++q) c[q] = cnt[min((int)threadIdx.x + q * kRT, nh - 1)];
-#pragma unroll
-    for (int q = 0; q < HC; ++q) hh[q] = hb[(int64_t)min((int)threadIdx.x + q * kRT, nh - 1) * hsh];
-    constexpr int U = 32768 / (kRefineNJ * kRT);    // 32768 pixels per keypoint preloaded
-    static_assert(U >= 1, "PVV_REFINE_NJ * PVV_REFINE_T must not exceed 32768 (preload depth)");
-    static_assert(kRT % 64 == 0 && kRT <= 1024, "PVV_REFINE_T: whole waves, at most 1024 threads");
-    // (guarded by the buffer's extent P, not by tn: the loads do not wait for
-    // tn's; records at t >= tn are read but never used)
-    const float4 *eb = pex + ((int64_t)b * vn + v) * P;
-    const int t0 = j * kRT + threadIdx.x, tstep = kRefineNJ * kRT;
-    float4 e[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) e[u] = eb[min(t0 + u * tstep, (int)P - 1)];
-    // argmax over h, first index on ties: key = count << 32 | ~h
-    uint64_t key = 0;
-    auto take = [&](int32_t cv, int h) {
-        const uint64_t k2 = ((uint64_t)(uint32_t)cv << 32) | (uint32_t)(0xffffffffu - (uint32_t)h);
-        key = k2 > key ? k2 : key;
-    };
-#pragma unroll
-    for (int q = 0; q < HC; ++q) {
-        const int h = (int)threadIdx.x + q * kRT;
-        take(h < nh ? c[q] : 0, h < nh ? h : -1);   // out of range: key 0 (the initial value)
-    }
-    if constexpr (BIG)
-        for (int h = (int)threadIdx.x + kRefineLdsHyp; h < nh; h += kRT) take(cnt[h], h);
-    if constexpr (lds_hyp)
-#pragma unroll
-        for (int q = 0; q < HC; ++q)
-            if ((int)threadIdx.x + q * kRT < nh) shyp[threadIdx.x + q * kRT] = hh[q];
-    key = row_max_u64(key);                      // DPP within 16-lane rows, rows through LDS
-    if ((lane_id() & 15) == 0) skey[threadIdx.x / 16] = key;
-    __syncthreads();
-    PVR_STAMP(1);
-    key = skey[0];
-#pragma unroll
-    for (int q = 1; q < kRT / 16; ++q) key = skey[q] > key ? skey[q] : key;
-    const int win = (int)(0xffffffffu - (uint32_t)key);
-    const int wcnt = (int)(key >> 32);
-    // RV:570-575: ratio = count / tn; best starts at 0 and is replaced only on a strict increase
-    const float ratio = n > 0 ? (float)wcnt / (float)n : 0.f;
-    float2 best = make_float2(0.f, 0.f);
-    if (n > 0 && 0.f < ratio) best = lds_hyp ? shyp[win] : hb[(int64_t)win * hsh];
-#ifdef PVV_TRACE
-    if (g_refine_trace) {   // trace builds: when the block's pixels have arrived
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        PVR_STAMP(7);
-    }
-#endif
-    double acc[5] = {0, 0, 0, 0, 0};
-    const bool fast = thr >= 1e-3f && thr <= 1.f;
-    const float thr2 = thr * thr;
-    // branch-free: the squared pre-test decides by selects; the exact sequence
-    // runs only when some lane of the wave is undecided; an outlier adds zeros
-    auto accum = [&](const float4 &q, bool valid) {   // (cx, cy, nx, ny)
-        bool inl, und;
-        refine_vote_pre(q.z, q.w, q.x, q.y, best.x, best.y, thr2, fast, &inl, &und);
-        und = und && valid;
-        if (__ballot(und)) {
-            if (und) inl = exact_vote(q.z, q.w, q.x, q.y, best.x, best.y, thr);
-        }
-        inl = inl && valid;
-        const float n0 = inl ? q.w : 0.f, n1 = inl ? -q.z : 0.f;   // RV:585-587 normal = (d_y, -d_x)
-        const float bb = inl ? q.w * q.x + -q.z * q.y : 0.f;       // RV:597 (2-term fp32 sum)
-        // f32 x f32 is exact in f64, so each fma equals the product-then-add
-        const double d0 = n0, d1 = n1, db = bb;
-        acc[0] = __fma_rn(d0, d0, acc[0]);
-        acc[1] = __fma_rn(d0, d1, acc[1]);
-        acc[2] = __fma_rn(d1, d1, acc[2]);
-        acc[3] = __fma_rn(d0, db, acc[3]);
-        acc[4] = __fma_rn(d1, db, acc[4]);
-    };
-#pragma unroll
-    for (int u = 0; u < U; ++u) accum(e[u], t0 + u * tstep < n);
-    for (int t = t0 + U * tstep; t < n; t += tstep) accum(eb[t], true);   // images larger than U * tstep
-    PVR_STAMP(2);
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const double sr = row_sum_d(acc[k]);
-        if ((lane_id() & 15) == 0) sacc[threadIdx.x / 16][k] = sr;
-    }
-    __syncthreads();
-    PVR_STAMP(3);
-    // ---- publish: this block's partial, the data as its own flag ----
-    const __amdgpu_buffer_rsrc_t sr = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(slot + (int64_t)b * vn * kRefineNJ * kRefineGran), (short)0, 0x7fffffff, 0x00020000);
-    static_assert(kRefineNJ <= 32, "gather: one pending bit per partial");
-    if (threadIdx.x < kRefineGran) {
-        const int k = threadIdx.x;
-        uint64_t bits;
-        if (k < 5) {
-            double sk = sacc[0][k];
-#pragma unroll
-            for (int q = 1; q < kRT / 16; ++q) sk += sacc[q][k];
-            bits = __builtin_bit_cast(uint64_t, sk);
-        } else {
-            bits = ((uint64_t)(uint32_t)(n > 0 ? win : 0) << 32) | __float_as_uint(ratio);
-        }
-        typedef int v4i __attribute__((ext_vector_type(4)));
-        const v4i g = {(int)(uint32_t)bits, (int)kRefineTag, (int)(uint32_t)(bits >> 32), (int)kRefineTag};
-        __builtin_amdgcn_raw_buffer_store_b128(g, sr, ((v * kRefineNJ + j) * kRefineGran + k) * 16, 0, 16);   // sc1
-    }
-    if (j == 0 && threadIdx.x == 0) {
-        if (diag.win_ratio) diag.win_ratio[b * vn + v] = n > 0 ? ratio : 0.f;
-        if (diag.win_idx) diag.win_idx[b * vn + v] = n > 0 ? win : 0;
-    }
-    PVR_STAMP(4);
-    // the image's highest block gathers: dispatched last (in practice: only
-    // speed depends on it), it mostly finds every partial already there
-    if (j != kRefineNJ - 1 || v != vn - 1) return;
-    // ---- gather.  Thread p polls value k of keypoint vv in a quarter of the
-    // kRefineNJ partials (its loads in flight together); sums in partial
-    // order, quarters then in order: deterministic ----
-    constexpr int kGQ = kRefineNJ >= 4 ? 4 : kRefineNJ, kGJ = kRefineNJ / kGQ;
-    __shared__ double sks[64][5];
-    __shared__ double sq[64 * kRefineGran * kGQ];
-    __shared__ float srat[64];
-    __shared__ int sflag;   // bit 0: some matrix singular, bit 1: gather gave up
-    if (threadIdx.x == 0) sflag = 0;
-    __syncthreads();
-    bool gave_up = false;
-    for (int p = threadIdx.x; p < vn * kRefineGran * kGQ; p += kRT) {
-        const int vk = p / kGQ, jq = p - vk * kGQ;
-        const int vv = vk / kRefineGran, k = vk - vv * kRefineGran;
-        const int base = (vv * kRefineNJ + jq * kGJ) * kRefineGran + k;
-        uint64_t val[kGJ];
-        uint32_t pend = (1u << kGJ) - 1;
-        for (uint32_t spins = 0; pend; ++spins) {
-            typedef int v4i __attribute__((ext_vector_type(4)));
-            v4i g[kGJ];
-#pragma unroll
-            for (int jj = 0; jj < kGJ; ++jj)
-                if (pend >> jj & 1) g[jj] = __builtin_amdgcn_raw_buffer_load_b128(sr, (base + jj * kRefineGran) * 16, 0, 16);
-#pragma unroll
-            for (int jj = 0; jj < kGJ; ++jj)
-                if ((pend >> jj & 1) && (uint32_t)g[jj].y == kRefineTag && (uint32_t)g[jj].w == kRefineTag) {
-                    val[jj] = ((uint64_t)(uint32_t)g[jj].z << 32) | (uint32_t)g[jj].x;
-                    pend &= ~(1u << jj);
-                }
-            if (pend && spins >= kRefineSpinMax) { gave_up = true; break; }
-            if (pend) __builtin_amdgcn_s_sleep(2);
-        }
-        if (gave_up) break;
-        if (k < 5) {
-            double sum = __builtin_bit_cast(double, val[0]);
-#pragma unroll
-            for (int jj = 1; jj < kGJ; ++jj) sum += __builtin_bit_cast(double, val[jj]);
-            sq[p] = sum;
-        } else if (jq == 0) {
-            srat[vv] = __uint_as_float((uint32_t)val[0]);   // every block of a keypoint finds the same winner
-        }
-    }
-    if (gave_up) sflag = 2;   // benign race: every writer stores 2
-    __syncthreads();
-    for (int q = threadIdx.x; q < vn * 5; q += kRT) {
-        const int vv = q / 5, k = q - vv * 5;
-        const double *sp = &sq[(vv * kRefineGran + k) * kGQ];
-        double sum = sp[0];
-#pragma unroll
-        for (int jq = 1; jq < kGQ; ++jq) sum += sp[jq];
-        sks[vv][k] = sum;
-    }
-    __syncthreads();
-    PVR_STAMP(5);
-    // ---- solve, one thread per keypoint (vn <= 64: wave 0) ----
-    const int vv = threadIdx.x;
-    const bool act = vv < vn;
-    float A00 = 0, A01 = 0, A11 = 0, B0 = 0, B1 = 0, rat = 3.0e38f;
-    float inv[4] = {1.f, 0.f, 0.f, 1.f};
-    if (act) {
-        A00 = (float)sks[vv][0]; A01 = (float)sks[vv][1]; A11 = (float)sks[vv][2];
-        B0 = (float)sks[vv][3]; B1 = (float)sks[vv][4];
-        rat = srat[vv];
-        if (!lu2_inv(A00, A01, A01, A11, inv)) atomicOr(&sflag, 1);
-    }
-    __syncthreads();
-    if (threadIdx.x >= 64) return;
-    const int flag = sflag;
-    if (flag & 1) { inv[0] = 1.f; inv[1] = 0.f; inv[2] = 0.f; inv[3] = 1.f; }   // RV:514-517
-    if (act) {
-        float x = inv[0] * B0 + inv[1] * B1;
-        float y = inv[2] * B0 + inv[3] * B1;
-        if (n == 0) { x = 0.f; y = 0.f; }
-        if (flag & 2) { x = __int_as_float(0x7fc00000); y = x; }   // gather gave up: loud
-        out[((int64_t)b * vn + vv) * 2] = x;
-        out[((int64_t)b * vn + vv) * 2 + 1] = y;
-        if (diag.ata) {
-            float *q = diag.ata + ((int64_t)b * vn + vv) * 4;
-            q[0] = A00; q[1] = A01; q[2] = A01; q[3] = A11;
-        }
-        if (diag.atb) { diag.atb[((int64_t)b * vn + vv) * 2] = B0; diag.atb[((int64_t)b * vn + vv) * 2 + 1] = B1; }
-    }
-    if (diag.tn && vv == 0) diag.tn[b] = n;
-    if (diag.iters) {
-        // min ratio over keypoints -> iterations the reference's `while True` would run
-        float r = rat;
-        for (int o = 32; o > 0; o >>= 1) r = fminf(r, __shfl_xor(r, o));
-        if (vv == 0) {
-            int it = 0;
-            if (n > 0) {
-                long long hyp_num = 0;
-                while (true) {
-                    hyp_num += nh;
-                    ++it;
-                    float val = 1.f - powf(1.f - r * r, (float)hyp_num);
-                    if (val > confidence || it > max_iter) break;
-                }
-            }
-            diag.iters[b] = it;
-        }
-    }
-    PVR_STAMP(6);
-}
-
-// ==========================================================================
-// ransac_motion_voting (RV:966-987): per image and keypoint, the mean over
-// the foreground (mask.byte() != 0) of vertex + (col, row) -- the vertex
-// field holds offsets here.  fp64 sums (torch.mean's fp32 order is
-// unspecified), block-local in LDS, then one device-scope add per block; the
-// last block of each image divides.  Empty foreground -> zeros (RV:977-979).
-// ==========================================================================
-template <int KIND>
-__global__ __launch_bounds__(256) void k_motion_vote(MaskView m, VertexView vx, int H, int W, int vn, double *acc,
-                                                     int32_t *cnt, int32_t *ticket, float *out) {
-    const int b = blockIdx.y, nblk = gridDim.x;
-    __shared__ double sacc[64 * 2];
-    __shared__ int scnt;
-    for (int i = threadIdx.x; i < vn * 2; i += 256) sacc[i] = 0.0;
-    if (threadIdx.x == 0) scnt = 0;
-    __syncthreads();
-    const uint32_t p = (uint32_t)blockIdx.x * 256 + threadIdx.x;
-    if (p < (uint32_t)H * W) {
-        const int r = (int)(p / (uint32_t)W), c = (int)(p - (uint32_t)r * W);
-        if (is_fg<KIND, false>(m, b, r, c)) {
-            atomicAdd(&scnt, 1);
-            const int64_t vo = b * vx.s[0] + r * vx.s[1] + c * vx.s[2];
-            for (int v = 0; v < vn; ++v) {
-                float dx, dy;
-                if (vx.kind == PV_VERTEX_F32) {
-                    dx = ((const float *)vx.p)[vo + v * vx.s[3]];
-                    dy = ((const float *)vx.p)[vo + v * vx.s[3] + vx.s[4]];
-                } else {
-                    dx = __half2float(((const __half *)vx.p)[vo + v * vx.s[3]]);
-                    dy = __half2float(((const __half *)vx.p)[vo + v * vx.s[3] + vx.s[4]]);
-                }
-                atomicAdd(&sacc[v * 2], (double)(dx + (float)c));       // RV:983 vertex + coords (fp32 add)
-                atomicAdd(&sacc[v * 2 + 1], (double)(dy + (float)r));
-            }
-        }
-    }
-    __syncthreads();
-    if (scnt) {
-        for (int i = threadIdx.x; i < vn * 2; i += 256) atomicAdd(&acc[(int64_t)b * vn * 2 + i], sacc[i]);
-        if (threadIdx.x == 0) atomicAdd(&cnt[b], scnt);
-    }
-    __syncthreads();
-    __shared__ int slast;
-    if (threadIdx.x == 0) {
-        __threadfence();
-        slast = __hip_atomic_fetch_add(&ticket[b], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == nblk - 1;
-    }
-    __syncthreads();
-    if (!slast) return;
-    const int n = ld_agent(&cnt[b]);
-    for (int i = threadIdx.x; i < vn * 2; i += 256)
-        out[(int64_t)b * vn * 2 + i] = n > 0 ? (float)(ld_agent(&acc[(int64_t)b * vn * 2 + i]) / n) : 0.f;
-}
-
-template <int KIND, bool EVD>
-struct MotionStage {
-    static int run(const MaskView *m, const VertexView *vx, int b, int H, int W, int vn, double *acc, int32_t *cnt,
-                   int32_t *ticket, float *out, hipStream_t s) {
-        dim3 grid((unsigned)(((int64_t)H * W + 255) / 256), (unsigned)b);
-        k_motion_vote<KIND><<<grid, 256, 0, s>>>(*m, *vx, H, W, vn, acc, cnt, ticket, out);
-        return PV_OK;
-    }
-};
-
-// ==========================================================================
-// v5 confidence (RV:856-858): the inlier ratio of each refined keypoint at
-// a second threshold (0.999), counted over the image's compacted pixels.
-// ==========================================================================
-__global__ __launch_bounds__(256) void k_point_conf(const float *pts, const float4 *pex, const int32_t *tn, int64_t P,
-                                                    int vn, float thr, int32_t *confc, float *conf) {
-    const int j = blockIdx.x, v = blockIdx.y, b = blockIdx.z;
-    const int n = min(max(tn[b], 0), (int)P);   // clamped like tn_at: loads stay inside the P records
-    __shared__ int sh[8];
-    const float px = pts[((int64_t)b * vn + v) * 2], py = pts[((int64_t)b * vn + v) * 2 + 1];
-    const float4 *eb = pex + ((int64_t)b * vn + v) * P;
-    int c = 0;
-    for (int t = j * 256 + threadIdx.x; t < n; t += kRefineNJ * 256) {
-        const float4 e = eb[t];   // (cx, cy, nx, ny)
-        c += exact_vote(e.z, e.w, e.x, e.y, px, py, thr) ? 1 : 0;
-    }
-    c = block_sum2(c, 0, sh).x;
-    if (threadIdx.x == 0) {
-        int32_t *cc = confc + ((int64_t)b * vn + v) * 2;
-        if (c) atomicAdd(&cc[0], c);
-        __threadfence();
-        const int t = __hip_atomic_fetch_add(&cc[1], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (t == kRefineNJ - 1) {
-            const int total = ld_agent(&cc[0]);
-            conf[(int64_t)b * vn + v] = n > 0 ? (float)total / (float)n : 0.f;   // RV:858 float division
-        }
-    }
-}
-
-// ==========================================================================
-// EVD (RV:333-406, RV:263-331): per (image, keypoint) over all hypotheses.
-// ==========================================================================
-__global__ __launch_bounds__(256) void k_evd_with_mean(const int32_t *counts, const float2 *hyp, const int32_t *fg,
-                                                       const int32_t *tn, int vn, int nh, int min_num,
-                                                       int min_hyp_num, const float *mean, float *cov) {
-    const int v = blockIdx.x, b = blockIdx.y;
-    const int fgb = fg[b];
-    const float mx = mean[(b * vn + v) * 2], my = mean[(b * vn + v) * 2 + 1];
-    __shared__ double sacc[4][4];
-    __shared__ float smax[4];
-    float *cv = cov + ((int64_t)b * vn + v) * 4;
-    if (fgb < min_num) {
-        // RV:343-348: min_hyp_num zero hypotheses with ratio 1 (all kept by the max-0.1 rule)
-        if (threadIdx.x == 0) {
-            double dx = (double)(0.f - mx), dy = (double)(0.f - my);
-            double w = (double)min_hyp_num;
-            float den = (float)w + 1e-3f;
-            cv[0] = (float)(w * dx * dx) / den;
-            cv[1] = (float)(w * dx * dy) / den;
-            cv[2] = (float)(w * dy * dx) / den;
-            cv[3] = (float)(w * dy * dy) / den;
-        }
-        return;
-    }
-    const float fgf = (float)tn[b];   // RV:355 foreground re-counted after downsampling == tn
-    const int32_t *cnt = counts + ((int64_t)b * vn + v) * nh;
-    float m = -1.f;
-    for (int h = threadIdx.x; h < nh; h += 256) m = fmaxf(m, (float)cnt[h] / fgf);
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if (lane_id() == 0) smax[threadIdx.x / 64] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
-    const float thresh = m - 0.1f;                                   // RV:394
-    double a[4] = {0, 0, 0, 0};
-    for (int h = threadIdx.x; h < nh; h += 256) {
-        float w = (float)cnt[h] / fgf;
-        if (w < thresh) w = 0.f;                                     // RV:395
-        float2 q = hyp[((int64_t)b * nh + h) * vn + v];
-        float dx = q.x - mx, dy = q.y - my;                          // RV:398
-        float wx = dx * w, wy = dy * w;                              // RV:399
-        a[0] += (double)dx * wx;
-        a[1] += (double)dx * wy;
-        a[2] += (double)dy * wy;
-        a[3] += (double)w;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        double s = wave_sum_d(a[k]);
-        if (lane_id() == 0) sacc[threadIdx.x / 64][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s[4];
-        for (int k = 0; k < 4; ++k) s[k] = sacc[0][k] + sacc[1][k] + sacc[2][k] + sacc[3][k];
-        float den = (float)s[3] + 1e-3f;                             // RV:401
-        cv[0] = (float)s[0] / den;
-        cv[1] = (float)s[1] / den;
-        cv[2] = (float)s[1] / den;
-        cv[3] = (float)s[2] / den;
-    }
-}
-
-// RV:320-329: top-k (ties: lowest index first) then weighted mean / covariance.
-__global__ __launch_bounds__(256) void k_evd_topk(const int32_t *counts, const float2 *hyp, const int32_t *fg,
-                                                  const int32_t *tn, int vn, int nh, int min_num, int topk,
-                                                  float *mean, float *cov) {
-    const int v = blockIdx.x, b = blockIdx.y;
-    const int fgb = fg[b];
-    float *mo = mean + ((int64_t)b * vn + v) * 2;
-    float *cv = cov + ((int64_t)b * vn + v) * 4;
-    if (fgb < min_num) {   // RV:276-281: zero hypotheses -> mean 0, cov 0
-        if (threadIdx.x == 0) { mo[0] = 0.f; mo[1] = 0.f; cv[0] = cv[1] = cv[2] = cv[3] = 0.f; }
-        return;
-    }
-    const float fgf = (float)tn[b];
-    const int32_t *cnt = counts + ((int64_t)b * vn + v) * nh;
-    __shared__ int sred[4];
-    __shared__ double sacc[4][6];
-    auto block_sum = [&](int x) {
-        x = wave_sum_i(x);
-        __syncthreads();
-        if (lane_id() == 0) sred[threadIdx.x / 64] = x;
-        __syncthreads();
-        return sred[0] + sred[1] + sred[2] + sred[3];
-    };
-    // k-th largest count T: largest T with #{count >= T} >= k (binary search on the value)
-    int k = min(topk, nh);
-    int lo = 0, hi = 0;
-    for (int h = threadIdx.x; h < nh; h += 256) hi = max(hi, cnt[h]);
-    for (int o = 32; o > 0; o >>= 1) hi = max(hi, __shfl_xor(hi, o));
-    __syncthreads();
-    if (lane_id() == 0) sred[threadIdx.x / 64] = hi;
-    __syncthreads();
-    hi = max(max(sred[0], sred[1]), max(sred[2], sred[3]));
-    while (lo < hi) {   // invariant: #{>= lo} >= k
-        int mid = (lo + hi + 1) / 2;
-        int c = 0;
-        for (int h = threadIdx.x; h < nh; h += 256) c += cnt[h] >= mid;
-        c = block_sum(c);
-        if (c >= k) lo = mid; else hi = mid - 1;
-    }
-    const int T = lo;
-    int ngt = 0;
-    for (int h = threadIdx.x; h < nh; h += 256) ngt += cnt[h] > T;
-    ngt = block_sum(ngt);
-    const int need_eq = k - ngt;   // take the first `need_eq` hypotheses with count == T (index order)
-    double a[6] = {0, 0, 0, 0, 0, 0};
-    // pass 1: weights, weighted sums of x, y (mean, RV:323-324)
-    int eq_base = 0;
-    for (int h0 = 0; h0 < nh; h0 += 256) {
-        int h = h0 + threadIdx.x;
-        int c = h < nh ? cnt[h] : -1;
-        bool eq = c == T;
-        // exclusive prefix of eq inside this 256-slab
-        uint64_t bal = ballot(eq);
-        int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-        __syncthreads();
-        if (lane_id() == 0) sred[threadIdx.x / 64] = __popcll(bal);
-        __syncthreads();
-        int woff = 0;
-        for (int q = 0; q < (int)(threadIdx.x / 64); ++q) woff += sred[q];
-        int slab = sred[0] + sred[1] + sred[2] + sred[3];
-        bool sel = (c > T) || (eq && eq_base + woff + below < need_eq);
-        if (h < nh && sel) {
-            float w = (float)c / fgf;
-            float2 q = hyp[((int64_t)b * nh + h) * vn + v];
-            a[0] += (double)w;
-            a[1] += (double)(w * q.x);
-            a[2] += (double)(w * q.y);
-        }
-        eq_base += slab;
-    }
-    for (int kk = 0; kk < 3; ++kk) {
-        double s = wave_sum_d(a[kk]);
-        if (lane_id() == 0) sacc[threadIdx.x / 64][kk] = s;
-    }
-    __syncthreads();
-    double W = sacc[0][0] + sacc[1][0] + sacc[2][0] + sacc[3][0];
-    double SX = sacc[0][1] + sacc[1][1] + sacc[2][1] + sacc[3][1];
-    double SY = sacc[0][2] + sacc[1][2] + sacc[2][2] + sacc[3][2];
-    const float wsum = (float)W;
-    const float mx = (float)SX / wsum, my = (float)SY / wsum;
-    // pass 2: covariance about the mean (RV:326-329), every hypothesis, zero weight if not selected
-    eq_base = 0;
-    double c3[3] = {0, 0, 0};
-    for (int h0 = 0; h0 < nh; h0 += 256) {
-        int h = h0 + threadIdx.x;
-        int c = h < nh ? cnt[h] : -1;
-        bool eq = c == T;
-        uint64_t bal = ballot(eq);
-        int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-        __syncthreads();
-        if (lane_id() == 0) sred[threadIdx.x / 64] = __popcll(bal);
-        __syncthreads();
-        int woff = 0;
-        for (int q = 0; q < (int)(threadIdx.x / 64); ++q) woff += sred[q];
-        int slab = sred[0] + sred[1] + sred[2] + sred[3];
-        bool sel = (c > T) || (eq && eq_base + woff + below < need_eq);
-        if (h < nh && sel) {
-            float w = (float)c / fgf;
-            float2 q = hyp[((int64_t)b * nh + h) * vn + v];
-            float dx = q.x - mx, dy = q.y - my;
-            c3[0] += (double)dx * (dx * w);
-            c3[1] += (double)dx * (dy * w);
-            c3[2] += (double)dy * (dy * w);
-        }
-        eq_base += slab;
-    }
-    __syncthreads();
-    for (int kk = 0; kk < 3; ++kk) {
-        double s = wave_sum_d(c3[kk]);
-        if (lane_id() == 0) sacc[threadIdx.x / 64][3 + kk] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s0 = sacc[0][3] + sacc[1][3] + sacc[2][3] + sacc[3][3];
-        double s1 = sacc[0][4] + sacc[1][4] + sacc[2][4] + sacc[3][4];
-        double s2 = sacc[0][5] + sacc[1][5] + sacc[2][5] + sacc[3][5];
-        mo[0] = mx; mo[1] = my;
-        cv[0] = (float)s0 / wsum;
-        cv[1] = (float)s1 / wsum;
-        cv[2] = (float)s1 / wsum;
-        cv[3] = (float)s2 / wsum;
-    }
-}
-
 // ==========================================================================
 // drop-in kernels on the reference layouts
 // ==========================================================================
@@ -2768,9 +1340,6 @@ __global__ __launch_bounds__(256) void k_generate_api(const float *direct, const
 // fast domain take it for their whole row.
 constexpr int kBytePix = 8;
 constexpr int kByteWin = kWave * kBytePix;      // bytes of a row per segment
-#ifndef PVV_BYTE_HB
-#define PVV_BYTE_HB 64
-#endif
 constexpr int kByteHB = PVV_BYTE_HB;             // hypothesis records per batch (rows per wave, <= 64)
 static_assert(kByteHB <= 64 && kByteHB % 16 == 0, "row masks are 64-bit; quarter blocks take 16 rows");
 constexpr uint32_t kQueuePerWave = 128;          // band pairs a wave queues for its end (LDS)
@@ -3470,23 +2039,6 @@ __global__ __launch_bounds__(256) void k_vote_vp(const float *direct, const floa
     if (fabsf(ad) > thr) inliers[gid] = 1;
 }
 
-// --------------------------------------------------------------------------
-// host helpers
-// --------------------------------------------------------------------------
-int cu_count() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
-inline int rc(hipError_t e) { return e == hipSuccess ? PV_OK : (int)e; }
-inline int last() { return rc(hipGetLastError()); }
 
 // Constants of the rotated-frame test (DESIGN.md "Exactness of the fast vote
 // test"): tau = sqrt(1-thr^2)/thr; band = gzf * B + gzr * D with
@@ -3550,26 +2102,6 @@ uint64_t *g_vote_trace = nullptr;   // trace builds only (pv_debug_set_vote_trac
 // that drops work.  The A/B measurements behind each default are in the
 // comments and DESIGN.md section 7; the variants measured and removed are in
 // DESIGN.md's appendix "Removed variants".
-#ifdef PVV_PROFILE
-// profiling builds only (tools/build_variant.py profile -DPVV_PROFILE): the
-// ablation bits in effect (pv_debug_set_ablation, set between captures by the
-// profiling tools; outputs wrong): 1 no k_compact, 2 no k_hyp_gen, 4 no vote,
-// 8 no refine, 16 no k_fg_count, 32 an empty launch in k_hyp_gen's place,
-// 64 k_vote_mfma's band pairs not re-checked, 128 found but not queued
-int g_abl = 0;
-#else
-constexpr int g_abl = 0;
-#endif
-#ifndef PVV_VM_BPC
-#define PVV_VM_BPC 3        // k_vote_mfma blocks per CU (tools/vm_ab.sh, 8 in flight: 4 -> 36.6k images/s, 3 -> 40.2k, 2 -> 39.7k)
-#endif
-#ifndef PVV_BYTES_XCD
-#define PVV_BYTES_XCD 1     // k_vote_bytes: XCD-contiguous item ranges (31.1 vs 31.9 us interleaved)
-#endif
-#ifndef PVV_BYTES_BAL
-#define PVV_BYTES_BAL 1     // k_vote_bytes: CU-balanced grid of full + quarter blocks (33.0 -> 31.1 us)
-#endif
-static_assert(PVV_VM_BPC >= 1 && PVV_VM_BPC <= 4, "k_vote_mfma: 1..4 blocks per CU");
 
 // Test hooks, not for production (not in pvvote.h, set only by explicit calls
 // between launches, never during a capture): which fused vote/count kernel
@@ -3615,77 +2147,6 @@ void launch_vote(const VoteArgs &va, int64_t pixel_steps, hipStream_t s) {
             <<<vote_grid_steps(pixel_steps, (const void *)k_vote_count<PREPPED, false>), 256, 0, s>>>(va);
 }
 
-struct Launch {
-    int kind;
-    bool evd;
-};
-
-
-template <template <int, bool> class F, typename... A>
-int dispatch_mask(int kind, bool evd, A... args) {
-    switch (kind) {
-#define PV_CASE(K)                                                    \
-    case K:                                                           \
-        return evd ? F<K, true>::run(args...) : F<K, false>::run(args...);
-        PV_CASE(PV_MASK_I64)
-        PV_CASE(PV_MASK_U8)
-        PV_CASE(PV_MASK_I32)
-        PV_CASE(PV_MASK_SEG_F32)
-        PV_CASE(PV_MASK_SEG_F16)
-#undef PV_CASE
-    default:
-        return PV_EINVAL;
-    }
-}
-
-struct CompactArgs {
-    MaskView m;
-    VertexView vx;
-    int b, H, W, vn, nblk, min_num, max_num;
-    uint64_t seed;
-    const uint8_t *keep;
-    Workspace ws;
-    HypGen hg;          // hg.nhb > 0: k_compact's first blocks make the hypotheses
-    hipStream_t s;
-};
-
-template <int KIND, bool EVD>
-struct CompactStage {
-    static int run(const CompactArgs *a) {
-        dim3 grid(a->nblk + a->hg.nhb, a->b);
-        static_assert(kFgWideCPB == 8, "grpcnt: groups of 8 chunks");
-        if (g_abl & 16) {
-        } else if ((int64_t)a->nblk * a->b > kFgWideAbove)
-            k_fg_count<KIND, EVD, kFgWideCPB><<<dim3((a->nblk + kFgWideCPB - 1) / kFgWideCPB, a->b), 256, 0, a->s>>>(
-                a->m, a->H, a->W, a->ws.blkcnt, a->ws.fgbits, a->ws.grpcnt, a->nblk, a->ws.counts, a->ws.zero_words);
-        else
-            k_fg_count<KIND, EVD, 1><<<dim3(a->nblk, a->b), 256, 0, a->s>>>(a->m, a->H, a->W, a->ws.blkcnt, a->ws.fgbits,
-                                                                          nullptr, a->nblk, a->ws.counts,
-                                                                          a->ws.zero_words);
-        if (g_abl & 1) return last();
-        if ((int64_t)a->nblk * a->b > kFgWideAbove) {
-            if (a->vx.kind == PV_VERTEX_F32)
-                k_compact<KIND, EVD, PV_VERTEX_F32, true><<<grid, 256, 0, a->s>>>(
-                    a->m, a->vx, a->H, a->W, a->vn, a->ws.blkcnt, a->ws.grpcnt, a->ws.fgbits, a->ws.dsagg, a->nblk, a->min_num,
-                    a->max_num, a->seed, a->keep, a->ws.tn, a->ws.fgtot, a->ws.pex, a->hg);
-            else
-                k_compact<KIND, EVD, PV_VERTEX_F16, true><<<grid, 256, 0, a->s>>>(
-                    a->m, a->vx, a->H, a->W, a->vn, a->ws.blkcnt, a->ws.grpcnt, a->ws.fgbits, a->ws.dsagg, a->nblk, a->min_num,
-                    a->max_num, a->seed, a->keep, a->ws.tn, a->ws.fgtot, a->ws.pex, a->hg);
-            return last();
-        }
-        if (a->vx.kind == PV_VERTEX_F32)
-            k_compact<KIND, EVD, PV_VERTEX_F32, false><<<grid, 256, 0, a->s>>>(a->m, a->vx, a->H, a->W, a->vn, a->ws.blkcnt, a->ws.grpcnt, a->ws.fgbits, a->ws.dsagg,
-                                                     a->nblk, a->min_num, a->max_num, a->seed, a->keep, a->ws.tn,
-                                                     a->ws.fgtot, a->ws.pex, a->hg);
-        else
-            k_compact<KIND, EVD, PV_VERTEX_F16, false><<<grid, 256, 0, a->s>>>(a->m, a->vx, a->H, a->W, a->vn, a->ws.blkcnt, a->ws.grpcnt, a->ws.fgbits, a->ws.dsagg,
-                                                     a->nblk, a->min_num, a->max_num, a->seed, a->keep, a->ws.tn,
-                                                     a->ws.fgtot, a->ws.pex, a->hg);
-        return last();
-    }
-};
-
 int check_desc(const pv_image_desc *img) {
     if (!img || !img->mask || !img->vertex) return PV_EINVAL;
     if (img->b <= 0 || img->H <= 0 || img->W <= 0 || img->vn <= 0 || img->vn > 64) return PV_EINVAL;
@@ -3695,6 +2156,30 @@ int check_desc(const pv_image_desc *img) {
     return PV_OK;
 }
 
+// The mask and vertex views of a call's images.  extent is left 0: front_half
+// works it out (the compaction's buffer loads need it), the motion path never
+// reads it.
+void image_views(const pv_image_desc *img, MaskView *m, VertexView *vx) {
+    *m = MaskView{img->mask, img->mask_strides[0], img->mask_strides[1], img->mask_strides[2], img->mask_strides[3]};
+    vx->p = img->vertex;
+    vx->kind = img->vertex_kind;
+    for (int i = 0; i < 5; ++i) vx->s[i] = img->vertex_strides[i];
+    vx->extent = 0;
+}
+
+// The vote kernels index their work in 32 bits: the vote units of one image
+// if every pixel were foreground (0: too many, the call is refused) ...
+int64_t vote_units_per_image(int vn, int nh, int64_t P) {
+    const int64_t per_img = (int64_t)vn * ((nh + kGroup - 1) / kGroup) * P;
+    return per_img >= (1ll << 31) ? 0 : per_img;
+}
+// ... and the images per vote launch such that this upper bound stays < 2^31
+int images_per_vote_launch(int b, int64_t per_img) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(b, ((1ll << 31) - 1) / per_img));
+}
+// the hypotheses by k_compact's first blocks (compact_hyp) instead of a k_hyp_gen launch
+bool hyp_fused(int nh, int nblk) { return hyp_pregen_used(nh) && nblk <= kHypMaxChunks; }
+
 // compaction + hypotheses + fused vote/count, shared by v3 and EVD
 int front_half(const pv_image_desc *img, const pv_vote_params *prm, int nh, bool evd, const Workspace &w,
                const pv_v3_diag &dg, hipStream_t s) {
@@ -3702,11 +2187,9 @@ int front_half(const pv_image_desc *img, const pv_vote_params *prm, int nh, bool
     const int64_t P = (int64_t)H * W;
     const int nblk = (int)((P + kCompactChunk - 1) / kCompactChunk);
     CompactArgs ca;
-    ca.m = MaskView{img->mask, img->mask_strides[0], img->mask_strides[1], img->mask_strides[2],
-                    img->mask_strides[3]};
-    ca.vx.p = img->vertex;
-    ca.vx.kind = img->vertex_kind;
-    for (int i = 0; i < 5; ++i) ca.vx.s[i] = img->vertex_strides[i];
+    ca.mask_kind = img->mask_kind;
+    ca.evd = evd;
+    image_views(img, &ca.m, &ca.vx);
     {   // bytes one image's view spans (the compaction's buffer-load range)
         const int64_t es = img->vertex_kind == PV_VERTEX_F32 ? 4 : 2;
         int64_t hi = 0;
@@ -3724,9 +2207,9 @@ int front_half(const pv_image_desc *img, const pv_vote_params *prm, int nh, bool
     ca.keep = prm->keep;
     ca.ws = w;
     ca.s = s;
-    if ((int64_t)vn * ((nh + kGroup - 1) / kGroup) * P >= (1ll << 31)) return PV_EINVAL;
-    // the hypotheses by k_compact's first blocks (compact_hyp) instead of a k_hyp_gen launch
-    const bool hfuse = hyp_pregen_used(nh) && nblk <= kHypMaxChunks && !(g_abl & 2);
+    const int64_t per_img = vote_units_per_image(vn, nh, P);
+    if (!per_img) return PV_EINVAL;
+    const bool hfuse = hyp_fused(nh, nblk) && !(g_abl & 2);
     ca.hg = HypGen{};
     if (hfuse) {
         ca.hg.nhb = (int)(((int64_t)nh * vn + 255) / 256);
@@ -3736,7 +2219,7 @@ int front_half(const pv_image_desc *img, const pv_vote_params *prm, int nh, bool
         ca.hg.hyp_out = w.hyp; ca.hg.hypv_out = w.hypv; ca.hg.diag_hyp = dg.hyp;
         ca.hg.keptbits = w.keptbits;
     }
-    int r = dispatch_mask<CompactStage>(img->mask_kind, evd, (const CompactArgs *)&ca);
+    int r = compact(ca);
     if (r) return r;
     if (dg.ev_compact_end) {
         hipError_t e = hipEventRecord((hipEvent_t)dg.ev_compact_end, s);
@@ -3773,11 +2256,7 @@ int front_half(const pv_image_desc *img, const pv_vote_params *prm, int nh, bool
         hipError_t e = hipEventRecord((hipEvent_t)dg.ev_vote_begin, s);
         if (e != hipSuccess) return rc(e);
     }
-    // the kernel indexes its work in 32 bits: images per launch such that the
-    // upper bound (every pixel of every image in the foreground) stays < 2^31
-    const int64_t per_img = (int64_t)vn * va.hgn * P;
-    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(b, ((1ll << 31) - 1) / per_img));
-    if (per_img >= (1ll << 31)) return PV_EINVAL;
+    const int chunk = images_per_vote_launch(b, per_img);
     for (int b0 = 0; b0 < b; b0 += chunk) {
         VoteArgs vc = va;
         const int nb = std::min(chunk, b - b0);
@@ -3812,7 +2291,7 @@ const char *pv_version(void) { return PV_VERSION; }
 const char *pv_build_config(void) {
     // (band, rw, hypgen, hypfuse, fg_cpb, compact_skip: switches since fixed, kept
     // as literals so that bench records stay comparable across rounds)
-    return "vote=k_vote_mfma(bpc=" PVV_STR(PVV_VM_BPC) ",wpe=" PVM_WPE_STR ",chunk=" PVV_STR(PVM_CHUNK) ",queue=" PVV_STR(PVM_QUEUE) ",band=2,rw=0/0/0)"
+    return "vote=k_vote_mfma(bpc=" PVV_STR(PVV_VM_BPC) ",wpe=" PVV_STR(PVM_WPE) ",chunk=" PVV_STR(PVM_CHUNK) ",queue=" PVV_STR(PVM_QUEUE) ",band=2,rw=0/0/0)"
            " hypgen=1 hypfuse=1"
            " refine=" PVV_STR(PVV_REFINE_NJ) "x" PVV_STR(PVV_REFINE_T)
            " fg_cpb=1/8 compact_skip=1"
@@ -3985,11 +2464,6 @@ int pv_debug_wave_minmax(const float *in, float *out, int32_t nwaves, pv_stream_
     return last();
 }
 
-// debug only (not in pvvote.h): the downsampling look-back counts every earlier
-// block itself instead of reading its count (tests of the fallback path)
-int pv_debug_lookback_self(int32_t on) {
-    return rc(hipMemcpyToSymbol(HIP_SYMBOL(g_lb_self), &on, sizeof(on)));
-}
 
 #ifdef PVV_PROFILE
 // profiling builds only (never during a capture): work left out of the next
@@ -4003,8 +2477,6 @@ int pv_debug_set_ablation(int32_t m) {
 #ifdef PVV_TRACE
 // trace builds only: per-wave timestamps of the next pipeline vote launches
 void pv_debug_set_vote_trace(uint64_t *buf) { g_vote_trace = buf; }
-// trace builds only: per-block phase stamps of the next k_refine_solve launches
-int pv_debug_set_refine_trace(uint64_t *buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_refine_trace), &buf, sizeof(buf)); }
 #endif
 // test hook (not in pvvote.h): which fused vote/count kernel the pipeline runs
 // (0 matrix-core k_vote_mfma, 1 VALU k_vote_count); returns the previous
@@ -4019,12 +2491,6 @@ int pv_debug_set_bytes_mode(int32_t dbg) {
 #ifdef PVVOTE_TRACE_U1
 int pv_debug_set_bytes_trace(uint64_t *buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_btrace), &buf, sizeof(buf)); }
 #endif
-#ifdef PVV_TRACE
-int pv_debug_compact_trace(int on, uint64_t *host, int n) {
-    if (host) return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_ctrace), sizeof(uint64_t) * (size_t)n);
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_ctrace_on), &on, sizeof(int));
-}
-#endif
 
 size_t pv_v3_workspace_size(int32_t b, int32_t H, int32_t W, int32_t vn, int32_t n_hyp) {
     if (b <= 0 || H <= 0 || W <= 0 || vn <= 0 || n_hyp <= 0) return 0;
@@ -4035,12 +2501,11 @@ int pv_v3_kernel_launches(int32_t b, int32_t H, int32_t W, int32_t vn, int32_t n
     if (b <= 0 || H <= 0 || W <= 0 || vn <= 0 || n_hyp <= 0) return 0;
     const int64_t P = (int64_t)H * W;
     const int nblk = (int)((P + kCompactChunk - 1) / kCompactChunk);
-    const int64_t per_img = (int64_t)vn * ((n_hyp + kGroup - 1) / kGroup) * P;
-    if (per_img >= (1ll << 31)) return 0;
-    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(b, ((1ll << 31) - 1) / per_img));
+    const int64_t per_img = vote_units_per_image(vn, n_hyp, P);
+    if (!per_img) return 0;
+    const int chunk = images_per_vote_launch(b, per_img);
     const bool pre = hyp_pregen_used(n_hyp);
-    const bool fuse = pre && nblk <= kHypMaxChunks;
-    return 2 + (pre && !fuse ? 1 : 0) + (b + chunk - 1) / chunk + 1;
+    return 2 + (pre && !hyp_fused(n_hyp, nblk) ? 1 : 0) + (b + chunk - 1) / chunk + 1;
 }
 
 int pv_ransac_voting_v3(const pv_image_desc *img, const pv_vote_params *prm, float *out, void *workspace,
@@ -4057,13 +2522,7 @@ int pv_ransac_voting_v3(const pv_image_desc *img, const pv_vote_params *prm, flo
     if ((r = front_half(img, prm, nh, false, w, dg, s))) return r;
     const int b = img->b, vn = img->vn;
     const int64_t P = (int64_t)img->H * img->W;
-    // hypotheses keypoint-major when the pipeline pre-generated them (coalesced), else the reference layout
-    const bool hv = hyp_pregen_used(nh);
-    auto *kref = nh > kRefineLdsHyp ? k_refine_solve<true> : k_refine_solve<false>;
-    if (!(g_abl & 8)) kref<<<dim3(kRefineNJ, vn, b), kRT, 0, s>>>(w.counts, hv ? w.hypv : w.hyp, (int64_t)nh * vn,
-                                                          hv ? nh : 1, hv ? 1 : vn, w.pex, w.tn, P, vn, nh,
-                                                          prm->inlier_thresh, w.refslot,
-                                                          prm->confidence, prm->max_iter, out, dg);
+    if (!(g_abl & 8)) launch_refine(w, hyp_pregen_used(nh), b, vn, nh, P, prm, out, dg, s);
     if ((r = last())) return r;
     if (dg.counts) {
         hipError_t e = hipMemcpyAsync(dg.counts, w.counts, sizeof(int32_t) * (size_t)b * vn * nh,
@@ -4081,8 +2540,7 @@ int pv_ransac_voting_v5(const pv_image_desc *img, const pv_vote_params *prm, flo
     if (r) return r;
     Workspace w = carve(workspace, img->b, img->H, img->W, img->vn, prm->round_hyp_num);
     const int64_t P = (int64_t)img->H * img->W;
-    k_point_conf<<<dim3(kRefineNJ, img->vn, img->b), 256, 0, (hipStream_t)stream>>>(out, w.pex, w.tn, P, img->vn,
-                                                                                     conf_thresh, w.confc, conf);
+    launch_point_conf(w, out, img->b, img->vn, P, conf_thresh, conf, (hipStream_t)stream);
     return last();
 }
 
@@ -4099,14 +2557,11 @@ int pv_ransac_motion_voting(const pv_image_desc *img, float *out, pv_stream_t st
     if (e != hipSuccess) return rc(e);
     e = hipMemsetAsync(scr, 0, bytes, s);
     if (e != hipSuccess) return rc(e);
-    MaskView m{img->mask, img->mask_strides[0], img->mask_strides[1], img->mask_strides[2], img->mask_strides[3]};
+    MaskView m;
     VertexView vx;
-    vx.p = img->vertex;
-    vx.kind = img->vertex_kind;
-    for (int i = 0; i < 5; ++i) vx.s[i] = img->vertex_strides[i];
+    image_views(img, &m, &vx);
     int32_t *cnt = (int32_t *)(scr + acc_bytes);
-    r = dispatch_mask<MotionStage>(img->mask_kind, false, (const MaskView *)&m, (const VertexView *)&vx, b, img->H,
-                                   img->W, vn, (double *)scr, cnt, cnt + b, out, s);
+    r = launch_motion(img->mask_kind, m, vx, b, img->H, img->W, vn, (double *)scr, cnt, cnt + b, out, s);
     if (r) return r;
     r = last();
     e = hipFreeAsync(scr, s);
@@ -4141,8 +2596,7 @@ int pv_estimate_voting_distribution_with_mean_diag(const pv_image_desc *img, con
     int nh = 0;
     int r = evd_front(img, prm, workspace, workspace_bytes, &w, &nh, s, diag);
     if (r) return r;
-    k_evd_with_mean<<<dim3(img->vn, img->b), 256, 0, s>>>(w.counts, w.hyp, w.fgtot, w.tn, img->vn, nh, prm->min_num,
-                                                          prm->min_hyp_num, mean, cov);
+    launch_evd_with_mean(w, img->b, img->vn, nh, prm->min_num, prm->min_hyp_num, mean, cov, s);
     return last();
 }
 
@@ -4161,8 +2615,7 @@ int pv_estimate_voting_distribution(const pv_image_desc *img, const pv_vote_para
     int nh = 0;
     int r = evd_front(img, prm, workspace, workspace_bytes, &w, &nh, s);
     if (r) return r;
-    k_evd_topk<<<dim3(img->vn, img->b), 256, 0, s>>>(w.counts, w.hyp, w.fgtot, w.tn, img->vn, nh, prm->min_num,
-                                                     prm->topk, mean, cov);
+    launch_evd_topk(w, img->b, img->vn, nh, prm->min_num, prm->topk, mean, cov, s);
     return last();
 }
 

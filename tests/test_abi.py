@@ -63,6 +63,42 @@ def test_default_build_exports_test_hooks_only(default_cdll):
         assert hasattr(default_cdll, name), name
 
 
+# What libpvvote.so exported (nm -D --defined-only) while the vote library was one
+# translation unit; the launchers between its translation units (namespace pvv)
+# are hidden, so the list holds still.
+PV_EXPORTS = """
+pv_build_config pv_conv3x3_ex_f16 pv_conv3x3_f16 pv_conv3x3_workspace_bytes pv_conv3x3_workspace_counter_bytes
+pv_conv64_f16 pv_conv_epilogue_f16 pv_conv_epilogue_f32 pv_debug_lookback_self pv_debug_mfma_sums
+pv_debug_set_bytes_mode pv_debug_set_vote_kernel pv_debug_wave_minmax pv_decoder_conv2s_f16 pv_decoder_conv4s_f16
+pv_decoder_tail_f16 pv_decoder_tail_split_f16 pv_device_arch pv_error_string pv_estimate_voting_distribution
+pv_estimate_voting_distribution_with_mean pv_estimate_voting_distribution_with_mean_diag pv_generate_hypothesis
+pv_generate_hypothesis_vp pv_head_f16 pv_head_f32 pv_ransac_motion_voting pv_ransac_voting_v3 pv_ransac_voting_v5
+pv_relu_maxpool_f16 pv_relu_maxpool_f32 pv_stem_conv_f16 pv_stem_pool_f16 pv_stream_capture_id pv_stream_create
+pv_stream_destroy pv_uncertainty_pnp pv_uncertainty_pnp_refine pv_upsample2x_cat_f16 pv_upsample2x_cat_f32
+pv_v3_kernel_launches pv_v3_workspace_size pv_version pv_vote_counts pv_voting_for_hypothesis
+pv_voting_for_hypothesis_vp
+""".split()
+# ... and the names that are not pv_*: pvconv.hip's k_stem (the one kernel outside an anonymous namespace) ...
+OTHER_EXPORTS = {"_Z6k_stem8StemArgs", "_Z21__device_stub__k_stem8StemArgs"}
+# ... and hipcc's own __hip_cuid_<hash>, one per translation unit: the hash is of the source's
+# path and the options, so it differs from checkout to checkout and only the count is pinned
+HIP_CUID = re.compile(r"__hip_cuid_[0-9a-f]+")
+
+
+def test_default_build_exports_exactly_the_abi(lib):
+    # an internal launcher that leaked, or an entry point that lost its extern "C", fails this
+    # (always the default build in the tree, which the `lib` fixture has built -- not a
+    # PVVOTE_LIB variant the fixture may have loaded: variants export their own hooks)
+    import subprocess
+    from pvnet_amd import build
+    out = subprocess.run(["nm", "-D", "--defined-only", os.path.join(REPO, "pvnet_amd", "libpvvote.so")],
+                         capture_output=True, text=True, check=True).stdout
+    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    cuid = {n for n in names if HIP_CUID.fullmatch(n)}
+    assert len(cuid) == len(build.SRCS)
+    assert names - cuid == set(PV_EXPORTS) | OTHER_EXPORTS
+
+
 def test_version_and_errors(lib):
     assert lib.pv_version().decode().startswith("pvvote")
     assert lib.pv_error_string(0) == b"ok"

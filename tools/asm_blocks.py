@@ -1,8 +1,19 @@
 """Debug: per-basic-block instruction counts of one kernel in the device
-assembly (python -m pvnet_amd.build asm output).  usage: asm_blocks.py NAME-SUBSTRING"""
+assembly of the translation unit that holds it.
+usage: asm_blocks.py NAME-SUBSTRING [TU.hip (default pvvote.hip: the vote kernels) | FILE.s]
+A TU is read from csrc/TU.gfx950.s, which pvnet_amd.build.asm(TU) writes; it is
+compiled again only if that file is older than the sources."""
+import os
 import sys
 
-s = open("pvnet_amd/csrc/pvvote.gfx950.s").read().split("\n")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pvnet_amd import build as B  # noqa: E402
+
+tu = sys.argv[2] if len(sys.argv) > 2 else "pvvote.hip"
+path = tu if tu.endswith(".s") else os.path.join(B.CSRC, os.path.splitext(tu)[0] + ".gfx950.s")
+if not tu.endswith(".s") and B.stale(path):
+    B.asm(tu)
+s = open(path).read().split("\n")
 key = sys.argv[1]
 start = next(i for i, l in enumerate(s) if l.startswith("_Z") and key in l and l.split(":")[0].endswith("E"))
 blocks, cur = [], ["entry", 0, 0, 0, 0, []]

@@ -17,5 +17,6 @@ for e in [e for e in extra if e.startswith("--src=")]:
     extra.remove(e)
 os.makedirs(os.path.join(B.REPO, "variants"), exist_ok=True)
 out = os.path.join(B.REPO, "variants", name + ".so")
-subprocess.check_call([B.hipcc(), *B.HIPCC_FLAGS, *extra, "-o", out, *srcs])
+# (-I: an ALT outside csrc/ still finds the shared pv_*.h headers)
+subprocess.check_call([B.hipcc(), *B.HIPCC_FLAGS, "-I", B.CSRC, *extra, "-o", out, *srcs])
 print(out)
