@@ -106,7 +106,24 @@ typedef struct pv_image_desc {
     int32_t vertex_kind;    /* PV_VERTEX_F32 / PV_VERTEX_F16 */
     int64_t vertex_strides[5];
     int32_t b, H, W, vn;
+    int32_t ncls;           /* 0: one object per image (everything above).  >= 1: multi-object, see below */
 } pv_image_desc;
+
+/* Multi-object images (ncls >= 1, at most 64; not in the reference, which loops over the classes with
+ * mask[bi] == k + 1, RV:273, RV:340): one label map and the keypoints of every class in one call.
+ *   - vn is the keypoints per class; vertex is [b,H,W,ncls*vn,2], class c's keypoints the channels
+ *     [c*vn, (c+1)*vn).
+ *   - PV_MASK_I64 / I32 / U8 are label maps: a pixel belongs to class c (0-based) iff its full label
+ *     value equals c + 1 (no byte truncation: 257 belongs to no class), for v3 and EVD alike; label 0
+ *     and labels above ncls belong to no class.
+ *   - PV_MASK_SEG_F32 / F16 are logits [b,ncls+1,H,W] (strides [b,c,h,w]); the label is torch.argmax
+ *     over the channels (the first maximum wins, NaN counts as the maximum).
+ *   - Outputs and every per-image array are indexed by the virtual image bv = bi*ncls + c: out
+ *     [b,ncls,vn,2], conf, mean, cov, every pv_v3_diag array, prm->idxs, prm->keep ([b*ncls,H,W]) and
+ *     the RNG keys -- the results are those of the same call on the stacked batch of b*ncls binary masks.
+ *   - The caller sizes the workspace with pv_v3_workspace_size(b*ncls, ...); the launches are
+ *     pv_v3_kernel_launches(b*ncls, ...).
+ *   - pv_ransac_motion_voting takes ncls == 0 only. */
 
 typedef struct pv_vote_params {
     int32_t round_hyp_num;  /* hypotheses per round (RV:520 round_hyp_num) */
@@ -139,6 +156,8 @@ typedef struct pv_v3_diag {
                              * k_compact, the call's first two kernels)                         */
 } pv_v3_diag;
 
+/* b: the images of the call; b*ncls (the virtual images) for a multi-object descriptor, here and in
+ * pv_v3_kernel_launches. */
 size_t pv_v3_workspace_size(int32_t b, int32_t H, int32_t W, int32_t vn, int32_t n_hyp);
 /* Kernel launches one pv_ransac_voting_v3 call of this shape makes (the graph nodes it adds when
  * captured): compaction (2), hypotheses (0 when k_compact makes them), vote (1 per 2^31-pair chunk),

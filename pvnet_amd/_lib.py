@@ -27,7 +27,7 @@ c_i32, c_i64, c_u64, c_f32, c_size, c_vp = (ctypes.c_int32, ctypes.c_int64, ctyp
 class ImageDesc(ctypes.Structure):
     _fields_ = [("mask", c_vp), ("mask_kind", c_i32), ("mask_strides", c_i64 * 4),
                 ("vertex", c_vp), ("vertex_kind", c_i32), ("vertex_strides", c_i64 * 5),
-                ("b", c_i32), ("H", c_i32), ("W", c_i32), ("vn", c_i32)]
+                ("b", c_i32), ("H", c_i32), ("W", c_i32), ("vn", c_i32), ("ncls", c_i32)]
 
 
 class VoteParams(ctypes.Structure):

@@ -189,7 +189,29 @@ struct VertexView {
     int kind;
     int64_t s[5];
     int32_t extent;     // bytes spanned by one image's [h,w,vn,2] view (< 2^31: buffer-load range)
+    // multi-object calls (ncls >= 1; 0: one object per image): the view holds
+    // ncls * vn keypoint channels, extent spans all of them, and the pipeline's
+    // image index is the virtual image bv = bi * ncls + c
+    int32_t ncls;
+    int64_t cs;         // elements between two classes' first channels (vn * s[3])
 };
+
+// Image `b`'s base (bytes from vx.p) and the bytes from there to the end of the
+// image's view: the buffer descriptor of its loads.  MC: b is a virtual image,
+// the base is shifted to its class's channels and the range shortened by as
+// much, so a clamped load still ends inside the tensor.
+template <bool MC>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t image_rsrc(const VertexView &vx, int b, int es) {
+    int64_t base = (int64_t)b * vx.s[0] * es;
+    int32_t range = vx.extent;
+    if constexpr (MC) {
+        const int bi = b / vx.ncls, c = b - bi * vx.ncls;
+        const int64_t shift = c * vx.cs * es;
+        base = (int64_t)bi * vx.s[0] * es + shift;
+        range = vx.extent - (int32_t)shift;
+    }
+    return __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)vx.p + base), (short)0, range, 0x00020000);
+}
 
 // --------------------------------------------------------------------------
 // workspace

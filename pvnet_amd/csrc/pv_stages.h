@@ -40,7 +40,8 @@ struct CompactArgs {
     bool evd;           // foreground predicate: EVD's `mask == 1` (else `mask.byte() != 0`)
     MaskView m;
     VertexView vx;
-    int b, H, W, vn, nblk, min_num, max_num;
+    int b, H, W, vn, nblk, min_num, max_num;   // b: the pipeline's images (b * ncls virtual ones when ncls > 0)
+    int ncls;           // classes of a multi-object call (mask = label map, k_label_count); 0: one object per image
     uint64_t seed;
     const uint8_t *keep;
     Workspace ws;

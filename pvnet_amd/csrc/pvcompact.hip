@@ -1,7 +1,10 @@
 // pvcompact.hip -- the pipeline's first stage: foreground count (k_fg_count),
 // row-major stream compaction of the foreground pixels with their
 // per-keypoint directions (k_compact) and, in k_compact's first blocks, the
-// hypotheses (compact_hyp).  Host entry: pvv::compact (pv_stages.h).  The
+// hypotheses (compact_hyp).  A multi-object call (pv_image_desc.ncls >= 1)
+// runs k_label_count in k_fg_count's place: one read of each pixel's label
+// for the ballots and counts of every class, the rest over b * ncls virtual
+// images.  Host entry: pvv::compact (pv_stages.h).  The
 // look-back test hook and the compaction trace live here with the device
 // globals they set: a __device__ global belongs in the translation unit of
 // both its kernels and its host-side setter (a global no host code of the
@@ -69,6 +72,101 @@ __global__ __launch_bounds__(256) void k_fg_count(MaskView m, int H, int W, int3
     }
 }
 
+// ==========================================================================
+// K1 of a multi-object call (ncls >= 1): every pixel's label read once -- the
+// label map's value, or the argmax over the ncls + 1 logit planes (first
+// maximum wins, NaN is the maximum: torch.argmax) -- and the ballots, chunk
+// counts and group sums of all ncls classes written as k_fg_count would have
+// for the stacked batch of b * ncls binary masks `label == c + 1` (virtual
+// image bv = bi * ncls + c).  Same grids as k_fg_count over (chunks, b).
+// Lane c of a wave keeps class c's ballot (ncls <= 64), so a wave stores a
+// chunk's ncls ballots with one instruction.
+// ==========================================================================
+constexpr int kLabelPlanes = 4;   // logit planes of a pixel in flight together
+
+template <int KIND>
+__device__ __forceinline__ int read_label(const MaskView &m, int ncls, int b, int r, int c) {
+    if constexpr (KIND == PV_MASK_SEG_F32 || KIND == PV_MASK_SEG_F16) {
+        const int64_t o = b * m.s0 + r * m.s2 + c * m.s3;
+        float best = 0.f;
+        int lab = 0;
+        for (int k0 = 0; k0 <= ncls; k0 += kLabelPlanes) {
+            float v[kLabelPlanes];
+#pragma unroll
+            for (int u = 0; u < kLabelPlanes; ++u) {
+                const int64_t q = o + (int64_t)min(k0 + u, ncls) * m.s1;   // clamped: none behind a branch
+                if constexpr (KIND == PV_MASK_SEG_F32) v[u] = ((const float *)m.p)[q];
+                else v[u] = __half2float(((const __half *)m.p)[q]);
+            }
+#pragma unroll
+            for (int u = 0; u < kLabelPlanes; ++u) {
+                const int k = k0 + u;
+                if (k == 0) best = v[u];
+                else if (k <= ncls && !isnan(best) && (isnan(v[u]) || v[u] > best)) { best = v[u]; lab = k; }
+            }
+        }
+        return lab;
+    } else {
+        const int64_t o = b * m.s0 + r * m.s1 + c * m.s2;
+        int64_t v;
+        if constexpr (KIND == PV_MASK_I64) v = ((const int64_t *)m.p)[o];
+        else if constexpr (KIND == PV_MASK_I32) v = ((const int32_t *)m.p)[o];
+        else v = ((const uint8_t *)m.p)[o];
+        return v >= 1 && v <= ncls ? (int)v : 0;   // the full value: 257 is no class
+    }
+}
+
+template <int KIND, int CPB>
+__global__ __launch_bounds__(256) void k_label_count(MaskView m, int H, int W, int ncls, int32_t *blkcnt,
+                                                     uint64_t *fgbits, int32_t *grpcnt, int nblk, int32_t *zero,
+                                                     int64_t zero_words) {
+    static_assert(kCompactChunk == 256, "one pixel per thread");
+    const int bi = blockIdx.y, wid = threadIdx.x / 64, lane = lane_id();
+    const int64_t P = (int64_t)H * W;
+    {   // zero counts + tickets of all b * ncls virtual images
+        int64_t g = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
+        int64_t G = (int64_t)gridDim.x * gridDim.y * 256;
+        for (int64_t i = g; i < zero_words; i += G) zero[i] = 0;
+    }
+    __shared__ int sh[CPB][4][64];   // [chunk][wave][class]
+    int lab[CPB];
+#pragma unroll
+    for (int k = 0; k < CPB; ++k) {
+        const int blk = blockIdx.x * CPB + k;
+        const int64_t p = (int64_t)blk * kCompactChunk + threadIdx.x;
+        const uint32_t pc = (uint32_t)min(p, P - 1);   // every load in range
+        const int v = read_label<KIND>(m, ncls, bi, (int)(pc / (uint32_t)W), (int)(pc % (uint32_t)W));
+        lab[k] = blk < nblk && p < P ? v : 0;
+    }
+#pragma unroll
+    for (int k = 0; k < CPB; ++k) {
+        const int blk = blockIdx.x * CPB + k;   // block-uniform
+        if (blk >= nblk) break;
+        uint64_t mine = 0;
+        for (int c = 0; c < ncls; ++c) {        // wave-uniform
+            const uint64_t bal = ballot(lab[k] == c + 1);
+            if (lane == c) mine = bal;
+        }
+        if (lane < ncls) {
+            fgbits[(((int64_t)bi * ncls + lane) * nblk + blk) * 4 + wid] = mine;
+            sh[k][wid][lane] = __popcll(mine);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < CPB * ncls; i += 256) {
+        const int k = i / ncls, c = i - k * ncls, blk = blockIdx.x * CPB + k;
+        if (blk < nblk) blkcnt[((int64_t)bi * ncls + c) * nblk + blk] = sh[k][0][c] + sh[k][1][c] + sh[k][2][c] + sh[k][3][c];
+    }
+    if (CPB > 1 && (int)threadIdx.x < ncls) {   // the block's sum per class: k_compact's image totals read these
+        const int c = threadIdx.x;
+        int g = 0;
+#pragma unroll
+        for (int k = 0; k < CPB; ++k)
+            if (blockIdx.x * CPB + k < nblk) g += sh[k][0][c] + sh[k][1][c] + sh[k][2][c] + sh[k][3][c];
+        grpcnt[((int64_t)bi * ncls + c) * gridDim.x + blockIdx.x] = g;
+    }
+}
+
 // foreground total of image b from the per-block counts (every block of K1b/K2 does this)
 __device__ __forceinline__ int2 image_totals(const int32_t *cnt, int nblk, int upto, int *sh) {
     int all = 0, pre = 0;
@@ -104,7 +202,7 @@ __device__ int g_lb_self;   // debug (pv_debug_lookback_self): every look-back c
 
 // one chunk (256 pixels) of image b: the whole of a k_compact block
 // (block-uniform early returns; sh holds 8 ints, wcnt 4, pos 256 with TASKS)
-template <int KIND, bool EVD, int VK, bool TASKS>
+template <int KIND, bool EVD, int VK, bool TASKS, bool MC>
 __device__ __forceinline__ void compact_chunk(const VertexView &vx, int H, int W, int vn, const int32_t *blkcnt,
                                               const int32_t *grpcnt, const uint64_t *fgbits, int32_t *dsagg,
                                               int nblk, int min_num, int max_num, uint64_t seed, const uint8_t *keep,
@@ -169,8 +267,7 @@ __device__ __forceinline__ void compact_chunk(const VertexView &vx, int H, int W
     // < 2 GiB)
     const int r = (int)(p / (uint32_t)W), c = (int)(p - (uint32_t)r * W);
     constexpr int ES = VK == PV_VERTEX_F32 ? 4 : 2;
-    const __amdgpu_buffer_rsrc_t vr = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)((const char *)vx.p + (int64_t)b * vx.s[0] * ES), (short)0, vx.extent, 0x00020000);
+    const __amdgpu_buffer_rsrc_t vr = image_rsrc<MC>(vx, b, ES);
     const int voff = (int)((r * vx.s[1] + c * vx.s[2]) * ES);
     float nx[kCompactKp], ny[kCompactKp];
     auto load_group = [&](int v0) {
@@ -343,7 +440,7 @@ __device__ __forceinline__ int select_bit(const uint64_t (&w)[4], int q) {
     return 255;
 }
 
-template <int KIND, bool EVD, int VK>
+template <int KIND, bool EVD, int VK, bool MC>
 __device__ void compact_hyp(const VertexView &vx, int H, int W, int nblk, const int32_t *blkcnt,
                             const uint64_t *fgbits, const int32_t *dsagg, int32_t *pre, int *sh, const HypGen &g,
                             int b, int hb) {
@@ -481,8 +578,7 @@ __device__ void compact_hyp(const VertexView &vx, int H, int W, int nblk, const 
         }
     }
     constexpr int ES = VK == PV_VERTEX_F32 ? 4 : 2;
-    const __amdgpu_buffer_rsrc_t vr = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)((const char *)vx.p + (int64_t)b * vx.s[0] * ES), (short)0, vx.extent, 0x00020000);
+    const __amdgpu_buffer_rsrc_t vr = image_rsrc<MC>(vx, b, ES);
     const int s4 = (int)(vx.s[4] * ES);
     float cx[2], cy[2], nx[2], ny[2];
 #pragma unroll
@@ -505,7 +601,7 @@ __device__ void compact_hyp(const VertexView &vx, int H, int W, int nblk, const 
 // written by (pixel, keypoint) tasks spread over the block instead of by the
 // pixel's own lane (configs[2]'s 32 network frames, ~8 % foreground: 69 us).
 // With g.nhb > 0 the grid's first g.nhb blocks per image make the hypotheses.
-template <int KIND, bool EVD, int VK, bool TASKS>
+template <int KIND, bool EVD, int VK, bool TASKS, bool MC = false>
 __global__ __launch_bounds__(256) void k_compact(MaskView, VertexView vx, int H, int W, int vn,
                                                  const int32_t *blkcnt, const int32_t *grpcnt,
                                                  const uint64_t *fgbits, int32_t *dsagg,
@@ -517,10 +613,10 @@ __global__ __launch_bounds__(256) void k_compact(MaskView, VertexView vx, int H,
     __shared__ uint16_t pos[TASKS ? kCompactChunk : 1];
     __shared__ int32_t pre[kHypMaxChunks + 1 + (kHypMaxChunks + 31) / 32];
     if ((int)blockIdx.x < g.nhb) {
-        compact_hyp<KIND, EVD, VK>(vx, H, W, nblk, blkcnt, fgbits, dsagg, pre, sh, g, (int)blockIdx.y, (int)blockIdx.x);
+        compact_hyp<KIND, EVD, VK, MC>(vx, H, W, nblk, blkcnt, fgbits, dsagg, pre, sh, g, (int)blockIdx.y, (int)blockIdx.x);
         return;
     }
-    compact_chunk<KIND, EVD, VK, TASKS>(vx, H, W, vn, blkcnt, grpcnt, fgbits, dsagg, nblk, min_num, max_num, seed, keep, tn,
+    compact_chunk<KIND, EVD, VK, TASKS, MC>(vx, H, W, vn, blkcnt, grpcnt, fgbits, dsagg, nblk, min_num, max_num, seed, keep, tn,
                                         fgtot, pex, (int)blockIdx.y, (int)blockIdx.x - g.nhb, sh, wcnt, pos,
                                         g.nhb > 0 ? g.keptbits : nullptr);
 }
@@ -552,10 +648,51 @@ struct CompactStage {
     }
 };
 
+// A multi-object call (a->ncls >= 1; a->b counts the b * ncls virtual images):
+// k_label_count in k_fg_count's place, then k_compact with the class offset in
+// its vertex view.  k_compact never reads the mask, so one mask kind's
+// instantiation serves all of them.
+template <int KIND>
+int compact_multi(const CompactArgs *a) {
+    const int bi = a->b / a->ncls;
+    const bool wide = (int64_t)a->nblk * a->b > kFgWideAbove;   // the same for both kernels
+    if (wide)
+        k_label_count<KIND, kFgWideCPB><<<dim3((a->nblk + kFgWideCPB - 1) / kFgWideCPB, bi), 256, 0, a->s>>>(
+            a->m, a->H, a->W, a->ncls, a->ws.blkcnt, a->ws.fgbits, a->ws.grpcnt, a->nblk, a->ws.counts,
+            a->ws.zero_words);
+    else
+        k_label_count<KIND, 1><<<dim3(a->nblk, bi), 256, 0, a->s>>>(a->m, a->H, a->W, a->ncls, a->ws.blkcnt,
+                                                                   a->ws.fgbits, nullptr, a->nblk, a->ws.counts,
+                                                                   a->ws.zero_words);
+    auto launch = [&](auto kernel) {
+        kernel<<<dim3(a->nblk + a->hg.nhb, a->b), 256, 0, a->s>>>(
+            a->m, a->vx, a->H, a->W, a->vn, a->ws.blkcnt, a->ws.grpcnt, a->ws.fgbits, a->ws.dsagg, a->nblk, a->min_num,
+            a->max_num, a->seed, a->keep, a->ws.tn, a->ws.fgtot, a->ws.pex, a->hg);
+    };
+    const bool f32 = a->vx.kind == PV_VERTEX_F32;
+    if (wide) f32 ? launch(k_compact<PV_MASK_I64, false, PV_VERTEX_F32, true, true>)
+                  : launch(k_compact<PV_MASK_I64, false, PV_VERTEX_F16, true, true>);
+    else f32 ? launch(k_compact<PV_MASK_I64, false, PV_VERTEX_F32, false, true>)
+             : launch(k_compact<PV_MASK_I64, false, PV_VERTEX_F16, false, true>);
+    return last();
+}
+
 }  // namespace
 
 namespace pvv __attribute__((visibility("hidden"))) {
-int compact(const CompactArgs &a) { return dispatch_mask<CompactStage>(a.mask_kind, a.evd, &a); }
+int compact(const CompactArgs &a) {
+    if (a.ncls > 0) {
+        switch (a.mask_kind) {
+        case PV_MASK_I64: return compact_multi<PV_MASK_I64>(&a);
+        case PV_MASK_U8: return compact_multi<PV_MASK_U8>(&a);
+        case PV_MASK_I32: return compact_multi<PV_MASK_I32>(&a);
+        case PV_MASK_SEG_F32: return compact_multi<PV_MASK_SEG_F32>(&a);
+        case PV_MASK_SEG_F16: return compact_multi<PV_MASK_SEG_F16>(&a);
+        default: return PV_EINVAL;
+        }
+    }
+    return dispatch_mask<CompactStage>(a.mask_kind, a.evd, &a);
+}
 }  // namespace pvv
 
 extern "C" {

@@ -2153,8 +2153,14 @@ int check_desc(const pv_image_desc *img) {
     if (img->H > 65535 || img->W > 65535) return PV_EINVAL;   // pixel centres pack into 16 bits
     if (img->mask_kind < PV_MASK_I64 || img->mask_kind > PV_MASK_SEG_F16) return PV_EINVAL;
     if (img->vertex_kind != PV_VERTEX_F32 && img->vertex_kind != PV_VERTEX_F16) return PV_EINVAL;
+    if (img->ncls < 0 || img->ncls > 64) return PV_EINVAL;
+    if ((int64_t)img->b * std::max(img->ncls, 1) > INT32_MAX) return PV_EINVAL;
     return PV_OK;
 }
+
+// the images the pipeline's stages after k_label_count see: one per (image,
+// class) of a multi-object call (the virtual image bv = bi * ncls + c)
+int pipeline_images(const pv_image_desc *img) { return img->b * std::max(img->ncls, 1); }
 
 // The mask and vertex views of a call's images.  extent is left 0: front_half
 // works it out (the compaction's buffer loads need it), the motion path never
@@ -2165,6 +2171,8 @@ void image_views(const pv_image_desc *img, MaskView *m, VertexView *vx) {
     vx->kind = img->vertex_kind;
     for (int i = 0; i < 5; ++i) vx->s[i] = img->vertex_strides[i];
     vx->extent = 0;
+    vx->ncls = img->ncls;
+    vx->cs = (int64_t)img->vn * img->vertex_strides[3];
 }
 
 // The vote kernels index their work in 32 bits: the vote units of one image
@@ -2183,17 +2191,18 @@ bool hyp_fused(int nh, int nblk) { return hyp_pregen_used(nh) && nblk <= kHypMax
 // compaction + hypotheses + fused vote/count, shared by v3 and EVD
 int front_half(const pv_image_desc *img, const pv_vote_params *prm, int nh, bool evd, const Workspace &w,
                const pv_v3_diag &dg, hipStream_t s) {
-    const int b = img->b, H = img->H, W = img->W, vn = img->vn;
+    const int b = pipeline_images(img), H = img->H, W = img->W, vn = img->vn;
     const int64_t P = (int64_t)H * W;
     const int nblk = (int)((P + kCompactChunk - 1) / kCompactChunk);
     CompactArgs ca;
+    ca.ncls = img->ncls;
     ca.mask_kind = img->mask_kind;
     ca.evd = evd;
     image_views(img, &ca.m, &ca.vx);
     {   // bytes one image's view spans (the compaction's buffer-load range)
         const int64_t es = img->vertex_kind == PV_VERTEX_F32 ? 4 : 2;
         int64_t hi = 0;
-        const int64_t dims[5] = {1, H, W, vn, 2};
+        const int64_t dims[5] = {1, H, W, (int64_t)vn * std::max(img->ncls, 1), 2};   // the whole image view
         for (int i = 1; i < 5; ++i) {
             if (ca.vx.s[i] < 0) return PV_EINVAL;
             hi += (dims[i] - 1) * ca.vx.s[i];
@@ -2514,13 +2523,13 @@ int pv_ransac_voting_v3(const pv_image_desc *img, const pv_vote_params *prm, flo
     if (r) return r;
     if (!prm || !out || prm->round_hyp_num <= 0) return PV_EINVAL;
     const int nh = prm->round_hyp_num;
-    Workspace w = carve(workspace, img->b, img->H, img->W, img->vn, nh);
+    Workspace w = carve(workspace, pipeline_images(img), img->H, img->W, img->vn, nh);
     if (!workspace || workspace_bytes < w.total) return PV_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     pv_v3_diag dg{};
     if (diag) dg = *diag;
     if ((r = front_half(img, prm, nh, false, w, dg, s))) return r;
-    const int b = img->b, vn = img->vn;
+    const int b = pipeline_images(img), vn = img->vn;
     const int64_t P = (int64_t)img->H * img->W;
     if (!(g_abl & 8)) launch_refine(w, hyp_pregen_used(nh), b, vn, nh, P, prm, out, dg, s);
     if ((r = last())) return r;
@@ -2538,9 +2547,9 @@ int pv_ransac_voting_v5(const pv_image_desc *img, const pv_vote_params *prm, flo
     if (!conf) return PV_EINVAL;
     int r = pv_ransac_voting_v3(img, prm, out, workspace, workspace_bytes, diag, stream);
     if (r) return r;
-    Workspace w = carve(workspace, img->b, img->H, img->W, img->vn, prm->round_hyp_num);
+    Workspace w = carve(workspace, pipeline_images(img), img->H, img->W, img->vn, prm->round_hyp_num);
     const int64_t P = (int64_t)img->H * img->W;
-    launch_point_conf(w, out, img->b, img->vn, P, conf_thresh, conf, (hipStream_t)stream);
+    launch_point_conf(w, out, pipeline_images(img), img->vn, P, conf_thresh, conf, (hipStream_t)stream);
     return last();
 }
 
@@ -2548,6 +2557,7 @@ int pv_ransac_motion_voting(const pv_image_desc *img, float *out, pv_stream_t st
     int r = check_desc(img);
     if (r) return r;
     if (!out || img->mask_kind == PV_MASK_SEG_F32 || img->mask_kind == PV_MASK_SEG_F16) return PV_EINVAL;
+    if (img->ncls > 0) return PV_EINVAL;   // one object per image only
     hipStream_t s = (hipStream_t)stream;
     const int b = img->b, vn = img->vn;
     // stream-ordered, zeroed scratch: sums [b][vn][2] f64, counts [b], tickets [b]
@@ -2575,7 +2585,7 @@ static int evd_front(const pv_image_desc *img, const pv_vote_params *prm, void *
     if (!prm || prm->round_hyp_num <= 0 || prm->min_hyp_num <= 0) return PV_EINVAL;
     int rounds = (prm->min_hyp_num + prm->round_hyp_num - 1) / prm->round_hyp_num;
     *nh = rounds * prm->round_hyp_num;
-    *w = carve(workspace, img->b, img->H, img->W, img->vn, *nh);
+    *w = carve(workspace, pipeline_images(img), img->H, img->W, img->vn, *nh);
     if (!workspace || workspace_bytes < w->total) return PV_EWORKSPACE;
     pv_v3_diag ev{};     // the diag's timing events only (bench.py's U4 line)
     if (diag) {
@@ -2596,7 +2606,7 @@ int pv_estimate_voting_distribution_with_mean_diag(const pv_image_desc *img, con
     int nh = 0;
     int r = evd_front(img, prm, workspace, workspace_bytes, &w, &nh, s, diag);
     if (r) return r;
-    launch_evd_with_mean(w, img->b, img->vn, nh, prm->min_num, prm->min_hyp_num, mean, cov, s);
+    launch_evd_with_mean(w, pipeline_images(img), img->vn, nh, prm->min_num, prm->min_hyp_num, mean, cov, s);
     return last();
 }
 
@@ -2615,7 +2625,7 @@ int pv_estimate_voting_distribution(const pv_image_desc *img, const pv_vote_para
     int nh = 0;
     int r = evd_front(img, prm, workspace, workspace_bytes, &w, &nh, s);
     if (r) return r;
-    launch_evd_topk(w, img->b, img->vn, nh, prm->min_num, prm->topk, mean, cov, s);
+    launch_evd_topk(w, pipeline_images(img), img->vn, nh, prm->min_num, prm->topk, mean, cov, s);
     return last();
 }
 

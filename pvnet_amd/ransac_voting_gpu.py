@@ -21,6 +21,11 @@ Behaviour kept from the reference:
   * least squares on the winner's inliers with ``b_inv``'s batch-wide
     identity fallback when any keypoint's matrix is singular (RV:503-518).
 
+Not in the reference: the ``*_multi`` layers take a multi-object frame -- one
+label map (or the network's ``C+1`` logits) and the keypoints of every class
+-- where the reference loops over the classes with ``mask[bi] == k + 1``
+(RV:273, RV:340); one call, the same kernel sequence.
+
 Differences (documented in DESIGN.md): the random draws come from a counter
 RNG seeded from torch's CPU generator, not from torch's device RNG (which
 cannot be reproduced anyway); fp32 least-squares sums are accumulated in fp64
@@ -39,7 +44,9 @@ from . import _lib
 __all__ = ["ransac_voting_layer_v3", "ransac_voting_layer_v5", "ransac_motion_voting",
            "estimate_voting_distribution_with_mean",
            "estimate_voting_distribution",
-           "b_inv", "ransac_voting_layer_v3_from_network", "VotingWorkspace"]
+           "b_inv", "ransac_voting_layer_v3_from_network", "VotingWorkspace",
+           "ransac_voting_layer_v3_multi", "ransac_voting_layer_v3_multi_from_network",
+           "estimate_voting_distribution_with_mean_multi"]
 
 _MASK_KIND = {torch.int64: _lib.PV_MASK_I64, torch.uint8: _lib.PV_MASK_U8, torch.bool: _lib.PV_MASK_U8,
               torch.int32: _lib.PV_MASK_I32}
@@ -200,6 +207,11 @@ def _params(round_hyp_num, inlier_thresh, confidence=0.99, max_iter=100, min_num
     return p
 
 
+def _lead(d):
+    """(leading dimensions of a descriptor's per-image arrays, their product)."""
+    return ((d.b,), d.b) if d.ncls == 0 else ((d.b, d.ncls), d.b * d.ncls)
+
+
 def _aux(x, dtype, device, shape, name):
     if x is None:
         return None
@@ -212,28 +224,30 @@ def _aux(x, dtype, device, shape, name):
 def _v3(d, mask, vertex, round_hyp_num, inlier_thresh, confidence, max_iter, min_num, max_num, _idxs, _keep, _diag,
         _seed, _workspace, out=None, conf_thresh=None):
     dev = vertex.device
-    b, h, w, vn = d.b, d.H, d.W, d.vn
-    idxs = _aux(_idxs, torch.int32, dev, (b, round_hyp_num, vn, 2), "_idxs")
-    keep = _aux(_keep, torch.uint8, dev, (b, h, w), "_keep")
+    h, w, vn = d.H, d.W, d.vn
+    # the leading dimensions of every per-image array: (b,), or (b, classes) for a multi-object descriptor
+    lead, nimg = _lead(d)
+    idxs = _aux(_idxs, torch.int32, dev, (*lead, round_hyp_num, vn, 2), "_idxs")
+    keep = _aux(_keep, torch.uint8, dev, (*lead, h, w), "_keep")
     prm = _params(round_hyp_num, inlier_thresh, confidence, max_iter, min_num, max_num, _seed, idxs, keep)
     L = _lib.load()
-    nbytes = L.pv_v3_workspace_size(b, h, w, vn, round_hyp_num)
+    nbytes = L.pv_v3_workspace_size(nimg, h, w, vn, round_hyp_num)
     work = _workspace or _default_ws
     if out is None:
-        out = torch.empty((b, vn, 2), dtype=torch.float32, device=dev)
+        out = torch.empty((*lead, vn, 2), dtype=torch.float32, device=dev)
     diag = None
     dt = {}
     if _diag is not None:
-        dt = dict(hyp=torch.empty((b, round_hyp_num, vn, 2), dtype=torch.float32, device=dev),
-                  counts=torch.empty((b, vn, round_hyp_num), dtype=torch.int32, device=dev),
-                  win_idx=torch.empty((b, vn), dtype=torch.int32, device=dev),
-                  win_ratio=torch.empty((b, vn), dtype=torch.float32, device=dev),
-                  tn=torch.empty((b,), dtype=torch.int32, device=dev),
-                  iters=torch.empty((b,), dtype=torch.int32, device=dev),
-                  ata=torch.empty((b, vn, 2, 2), dtype=torch.float32, device=dev),
-                  atb=torch.empty((b, vn, 2), dtype=torch.float32, device=dev))
+        dt = dict(hyp=torch.empty((*lead, round_hyp_num, vn, 2), dtype=torch.float32, device=dev),
+                  counts=torch.empty((*lead, vn, round_hyp_num), dtype=torch.int32, device=dev),
+                  win_idx=torch.empty((*lead, vn), dtype=torch.int32, device=dev),
+                  win_ratio=torch.empty((*lead, vn), dtype=torch.float32, device=dev),
+                  tn=torch.empty(lead, dtype=torch.int32, device=dev),
+                  iters=torch.empty(lead, dtype=torch.int32, device=dev),
+                  ata=torch.empty((*lead, vn, 2, 2), dtype=torch.float32, device=dev),
+                  atb=torch.empty((*lead, vn, 2), dtype=torch.float32, device=dev))
         diag = _lib.V3Diag(**{k: v.data_ptr() for k, v in dt.items()})
-    conf = None if conf_thresh is None else torch.empty((b, vn), dtype=torch.float32, device=dev)
+    conf = None if conf_thresh is None else torch.empty((*lead, vn), dtype=torch.float32, device=dev)
     ws = work.get(dev, nbytes)
     with torch.cuda.device(dev):
         try:
@@ -309,17 +323,19 @@ def ransac_voting_layer_v3_from_network(seg_pred, vertex_pred, round_hyp_num, in
 
 
 def _evd_common(mask, vertex, round_hyp_num, min_hyp_num, inlier_thresh, min_num, max_num, topk, _idxs, _keep,
-                _seed, _workspace):
-    d = _desc(mask, vertex)
+                _seed, _workspace, d=None):
+    if d is None:
+        d = _desc(mask, vertex)
     dev = vertex.device
     rounds = int(np.ceil(min_hyp_num / round_hyp_num))
     nh = rounds * round_hyp_num
-    idxs = _aux(_idxs, torch.int32, dev, (d.b, nh, d.vn, 2), "_idxs")
-    keep = _aux(_keep, torch.uint8, dev, (d.b, d.H, d.W), "_keep")
+    lead, nimg = _lead(d)
+    idxs = _aux(_idxs, torch.int32, dev, (*lead, nh, d.vn, 2), "_idxs")
+    keep = _aux(_keep, torch.uint8, dev, (*lead, d.H, d.W), "_keep")
     prm = _params(round_hyp_num, inlier_thresh, 0.99, 100, min_num, max_num, _seed, idxs, keep,
                   min_hyp_num=min_hyp_num, topk=topk)
     L = _lib.load()
-    nbytes = L.pv_v3_workspace_size(d.b, d.H, d.W, d.vn, nh)
+    nbytes = L.pv_v3_workspace_size(nimg, d.H, d.W, d.vn, nh)
     return d, prm, nbytes, (idxs, keep), _workspace or _default_ws
 
 
@@ -363,6 +379,129 @@ def estimate_voting_distribution(mask, vertex, round_hyp_num=256, min_hyp_num=40
         finally:
             work.done(dev)
     _lib.check(code, "estimate_voting_distribution")
+    return mean, cov
+
+
+# --------------------------------------------------------------------------
+# multi-object frames: one label map, the keypoints of every class in one call
+# (the reference loops over the classes with mask[bi] == k + 1, RV:273, RV:340)
+# --------------------------------------------------------------------------
+_LABEL_KIND = {torch.int64: _lib.PV_MASK_I64, torch.uint8: _lib.PV_MASK_U8, torch.int32: _lib.PV_MASK_I32}
+
+
+def _desc_multi(label, vertex, class_num, seg=False):
+    """The descriptor of a multi-object call.  Shapes and dtypes are checked
+    first (on any device), then that the tensors are on one ROCm device."""
+    if not (isinstance(vertex, torch.Tensor) and isinstance(label, torch.Tensor)):
+        raise RuntimeError("label and vertex must be tensors")
+    class_num = int(class_num)
+    if not 1 <= class_num <= 64:
+        raise RuntimeError(f"class_num must be in [1, 64], got {class_num}")
+    if vertex.dim() != 5 or vertex.shape[4] != 2:
+        raise RuntimeError("vertex must be [b,h,w,class_num*vn,2]")
+    b, h, w, ch, _ = vertex.shape
+    if ch == 0 or ch % class_num != 0:
+        raise RuntimeError(f"vertex has {ch} keypoint channels, not divisible by class_num = {class_num}")
+    if ch // class_num > 64:
+        raise RuntimeError("at most 64 keypoints per class")
+    if vertex.dtype not in _VERTEX_KIND:
+        raise RuntimeError(f"vertex dtype {vertex.dtype} not supported (float32/float16)")
+    if seg:
+        if label.dim() != 4 or label.shape[1] != class_num + 1 or (label.shape[0], *label.shape[2:]) != (b, h, w):
+            raise RuntimeError(f"seg_pred must be [b,class_num+1,h,w] = {(b, class_num + 1, h, w)}, "
+                               f"got {tuple(label.shape)}")
+        if label.dtype not in _SEG_KIND:
+            raise RuntimeError(f"seg_pred dtype {label.dtype} not supported")
+    else:
+        if tuple(label.shape) != (b, h, w):
+            raise RuntimeError(f"label must be [b,h,w] = {(b, h, w)}, got {tuple(label.shape)}")
+        if label.dtype not in _LABEL_KIND:
+            raise RuntimeError(f"label dtype {label.dtype} not supported (int64/int32/uint8)")
+    if not vertex.is_cuda:
+        raise RuntimeError("vertex must be a CUDA tensor")
+    if not label.is_cuda:
+        raise RuntimeError(("seg_pred" if seg else "label") + " must be a CUDA tensor")
+    if label.device != vertex.device:
+        raise RuntimeError("label and vertex must be on the same device")
+    d = _lib.ImageDesc()
+    d.mask = label.data_ptr()
+    d.mask_kind = (_SEG_KIND if seg else _LABEL_KIND)[label.dtype]
+    for i in range(label.dim()):
+        d.mask_strides[i] = label.stride(i)
+    d.vertex = vertex.data_ptr()
+    d.vertex_kind = _VERTEX_KIND[vertex.dtype]
+    for i in range(5):
+        d.vertex_strides[i] = vertex.stride(i)
+    d.b, d.H, d.W, d.vn, d.ncls = b, h, w, ch // class_num, class_num
+    return d
+
+
+def ransac_voting_layer_v3_multi(label, vertex, class_num, round_hyp_num, inlier_thresh=0.99, confidence=0.99,
+                                 max_iter=100, min_num=100, max_num=30000, *, _idxs=None, _keep=None, _diag=None,
+                                 _seed=None, _workspace=None):
+    """``ransac_voting_layer_v3`` for every class of a multi-object frame in
+    one call: label [b,h,w] (int64/int32/uint8; a pixel belongs to class c iff
+    its label equals c + 1, 0 and labels above class_num to none), vertex
+    [b,h,w,class_num*vn,2] (f32 or f16, any strides; class c's keypoints are
+    channels [c*vn, (c+1)*vn)) -> f32 [b,class_num,vn,2]: what v3 gives for
+    ``label == c + 1`` and that slice of vertex, zeros for a class with fewer
+    than ``min_num`` pixels.
+
+    Test hooks: ``_idxs`` [b,class_num,hn,vn,2], ``_keep`` [b,class_num,h,w],
+    ``_diag`` (tensors with leading [b,class_num]), ``_seed``."""
+    d = _desc_multi(label, vertex, class_num)
+    return _v3(d, label, vertex, round_hyp_num, inlier_thresh, confidence, max_iter, min_num, max_num, _idxs,
+               _keep, _diag, _seed, _workspace)
+
+
+def ransac_voting_layer_v3_multi_from_network(seg_pred, vertex_pred, class_num, round_hyp_num, inlier_thresh=0.99,
+                                              confidence=0.99, max_iter=100, min_num=100, max_num=30000, *,
+                                              _idxs=None, _keep=None, _diag=None, _seed=None, _workspace=None,
+                                              out=None):
+    """The multi-object network's outputs straight in: seg_pred
+    [b,class_num+1,h,w] logits and vertex_pred [b,2*class_num*vn,h,w] (f32 or
+    f16, any strides).  The argmax over the channels (torch.argmax: first
+    maximum, NaN is the maximum) and the permute/view are done inside the
+    kernels -> f32 [b,class_num,vn,2]."""
+    if not (isinstance(vertex_pred, torch.Tensor) and vertex_pred.dim() == 4):
+        raise RuntimeError("vertex_pred must be [b,2*class_num*vn,h,w]")
+    b, c, h, w = vertex_pred.shape
+    if c % 2 != 0:
+        raise RuntimeError(f"vertex_pred has {c} channels, not 2*class_num*vn")
+    vertex = vertex_pred.permute(0, 2, 3, 1).unflatten(3, (c // 2, 2))
+    d = _desc_multi(seg_pred, vertex, class_num, seg=True)
+    if out is not None and (tuple(out.shape) != (b, d.ncls, d.vn, 2) or out.dtype != torch.float32
+                            or not out.is_contiguous() or out.device != vertex.device):
+        raise RuntimeError("out must be a contiguous f32 [b,class_num,vn,2] tensor on the inputs' device")
+    return _v3(d, seg_pred, vertex, round_hyp_num, inlier_thresh, confidence, max_iter, min_num, max_num, _idxs,
+               _keep, _diag, _seed, _workspace, out=out)
+
+
+def estimate_voting_distribution_with_mean_multi(label, vertex, mean, class_num, round_hyp_num=256,
+                                                 min_hyp_num=4096, topk=128, inlier_thresh=0.99, min_num=20,
+                                                 max_num=30000, *, _idxs=None, _keep=None, _seed=None,
+                                                 _workspace=None):
+    """``estimate_voting_distribution_with_mean`` for every class of a
+    multi-object frame: label and vertex as ``ransac_voting_layer_v3_multi``,
+    mean [b,class_num,vn,2] -> (mean, cov [b,class_num,vn,2,2]).  ``_idxs`` is
+    [b,class_num,rounds*round_hyp_num,vn,2]."""
+    d = _desc_multi(label, vertex, class_num)
+    d, prm, nbytes, keepalive, work = _evd_common(label, vertex, round_hyp_num, min_hyp_num, inlier_thresh, min_num,
+                                                  max_num, topk, _idxs, _keep, _seed, _workspace, d=d)
+    dev = vertex.device
+    if not isinstance(mean, torch.Tensor) or tuple(mean.shape) != (d.b, d.ncls, d.vn, 2):
+        raise RuntimeError("mean must be [b,class_num,vn,2]")
+    mean_c = mean.to(device=dev, dtype=torch.float32).contiguous()
+    cov = torch.empty((d.b, d.ncls, d.vn, 2, 2), dtype=torch.float32, device=dev)
+    ws = work.get(dev, nbytes)
+    with torch.cuda.device(dev):
+        try:
+            code = _lib.load().pv_estimate_voting_distribution_with_mean(
+                ctypes.byref(d), ctypes.byref(prm), mean_c.data_ptr(), cov.data_ptr(), ws.data_ptr(), nbytes,
+                torch.cuda.current_stream(dev).cuda_stream)
+        finally:
+            work.done(dev)
+    _lib.check(code, "estimate_voting_distribution_with_mean_multi")
     return mean, cov
 
 
