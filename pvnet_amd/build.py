@@ -1,9 +1,9 @@
-"""Build libpvvote.so (the HIP C-ABI library) in-tree for gfx950.
+"""Build libpvvote.so and libpveval.so (the HIP C-ABI libraries) in-tree for gfx950.
 
     python -m pvnet_amd.build            # or __graft_entry__.build()
 
-hipcc cross-compiles without a GPU.  The .so lands next to this file so it
-travels to the GPU box with the repository snapshot.
+hipcc cross-compiles without a GPU.  The libraries land next to this file so they
+travel to the GPU box with the repository snapshot.
 """
 from __future__ import annotations
 
@@ -20,6 +20,11 @@ SRCS = [os.path.join(CSRC, n) for n in (
     "pvvote.hip", "pvcompact.hip", "pvrefine.hip", "pvevd.hip", "pvpnp.hip", "pvdecoder.hip", "pvconv.hip")]
 HDR = os.path.join(REPO, "include", "pvvote.h")
 OUT = os.path.join(HERE, "libpvvote.so")
+# the pose-evaluation library (include/pveval.h): a library of its own, so libpvvote.so's
+# export list and translation-unit count hold still
+EVAL_SRCS = [os.path.join(CSRC, "pveval.hip")]
+EVAL_HDR = os.path.join(REPO, "include", "pveval.h")
+EVAL_OUT = os.path.join(HERE, "libpveval.so")
 ARCH = os.environ.get("PVVOTE_ARCH", "gfx950")
 
 HIPCC_FLAGS = [
@@ -51,26 +56,35 @@ def hipcc() -> str:
 
 
 def stale(out: str) -> bool:
-    """Is `out` missing, or older than any source under csrc/, the public header or this file?"""
+    """Is `out` missing, or older than any source under csrc/, a public header or this file?
+    For the two libraries the other one's translation units and public header do not count."""
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
+    other = {OUT: (*EVAL_SRCS, EVAL_HDR), EVAL_OUT: tuple(SRCS)}.get(out, ())
     deps = [os.path.join(CSRC, n) for n in os.listdir(CSRC) if n.endswith((".hip", ".h"))]
-    return any(os.path.getmtime(p) > t for p in (*deps, HDR, __file__))
+    return any(os.path.getmtime(p) > t for p in (*deps, HDR, EVAL_HDR, __file__) if p not in other)
 
 
 def needs_build() -> bool:
-    return stale(OUT)
+    return stale(OUT) or stale(EVAL_OUT)
+
+
+def _link(out: str, srcs, extra=()) -> None:
+    cmd = [hipcc(), *HIPCC_FLAGS, *extra, "-o", out + ".tmp", *srcs]
+    subprocess.check_call(cmd)
+    # every reference resolved (an unresolved kernel stub only shows at load time)
+    import ctypes
+    ctypes.CDLL(os.path.abspath(out + ".tmp"), mode=ctypes.RTLD_LOCAL | os.RTLD_NOW)
+    os.replace(out + ".tmp", out)
 
 
 def build(force: bool = False, extra=()) -> str:
-    if force or needs_build():
-        cmd = [hipcc(), *HIPCC_FLAGS, *extra, "-o", OUT + ".tmp", *SRCS]
-        subprocess.check_call(cmd)
-        # every reference resolved (an unresolved kernel stub only shows at load time)
-        import ctypes
-        ctypes.CDLL(os.path.abspath(OUT + ".tmp"), mode=ctypes.RTLD_LOCAL | os.RTLD_NOW)
-        os.replace(OUT + ".tmp", OUT)
+    """Build libpvvote.so and libpveval.so (each when stale); returns libpvvote.so's path."""
+    if force or stale(OUT):
+        _link(OUT, SRCS, extra)
+    if force or stale(EVAL_OUT):
+        _link(EVAL_OUT, EVAL_SRCS, extra)
     return OUT
 
 

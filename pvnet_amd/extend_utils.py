@@ -144,6 +144,41 @@ def uncertainty_pnp_v2(points_2d, covars, points_3d, camera_matrix, type="single
     return _single(points_2d, covars, points_3d, camera_matrix, "cov_v2")
 
 
+def find_nearest_point_idx_batch(ref_pts: torch.Tensor, que_pts: torch.Tensor) -> torch.Tensor:
+    """Batched device form of :func:`find_nearest_point_idx`: ref [b, pn1, dim], que [b, pn2, dim]
+    (dim 2 or 3) -> int32 [b, pn2], the lowest index of the nearest reference of each query
+    (include/pveval.h states the fp32 arithmetic), on the inputs' device and current stream."""
+    from . import _eval_lib
+    if ref_pts.device.type != "cuda" or que_pts.device != ref_pts.device:
+        raise RuntimeError("ref_pts and que_pts must be tensors on the same ROCm device")
+    if ref_pts.dim() != 3 or que_pts.dim() != 3 or ref_pts.shape[2] not in (2, 3) or \
+            que_pts.shape[2] != ref_pts.shape[2] or que_pts.shape[0] != ref_pts.shape[0]:
+        raise RuntimeError("ref_pts must be [b, pn1, dim] and que_pts [b, pn2, dim] with dim 2 or 3")
+    b, pn1, dim = (int(n) for n in ref_pts.shape)
+    pn2 = int(que_pts.shape[1])
+    if pn1 < 1:
+        raise RuntimeError("find_nearest_point_idx needs at least one reference point")
+    dev = ref_pts.device
+    ref = ref_pts.to(torch.float32).contiguous()
+    que = que_pts.to(torch.float32).contiguous()
+    idx = torch.empty((b, pn2), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _eval_lib.check(_eval_lib.load().pv_nearest_point_idx(ref.data_ptr(), que.data_ptr(), idx.data_ptr(), b, pn1,
+                                                              pn2, dim, torch.cuda.current_stream(dev).cuda_stream),
+                        "pv_nearest_point_idx")
+    return idx
+
+
+def find_nearest_point_idx(ref_pts, que_pts):
+    """extend_utils.py's find_nearest_point_idx (the cffi wrapper of
+    src/nearest_neighborhood.cu:48,84): ref_pts [pn1, dim], que_pts [pn2, dim] numpy,
+    dim 2 or 3 -> int32 [pn2], on the current ROCm device."""
+    dev = _device()
+    ref = torch.from_numpy(np.ascontiguousarray(ref_pts, np.float32)).to(dev)[None]
+    que = torch.from_numpy(np.ascontiguousarray(que_pts, np.float32)).to(dev)[None]
+    return find_nearest_point_idx_batch(ref, que)[0].cpu().numpy()
+
+
 def pose_from_voting(mean: torch.Tensor, cov: torch.Tensor, points_3d, camera_matrix) -> torch.Tensor:
     """Evaluator.evaluate_uncertainty's pose step (evaluation_utils.py:161-187)
     for a batch: keypoints [b, vn, 2] and covariances [b, vn, 2, 2] from
