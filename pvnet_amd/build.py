@@ -1,4 +1,4 @@
-"""Build libpvvote.so and libpveval.so (the HIP C-ABI libraries) in-tree for gfx950.
+"""Build libpvvote.so, libpveval.so and libpvpose.so (the HIP C-ABI libraries) in-tree for gfx950.
 
     python -m pvnet_amd.build            # or __graft_entry__.build()
 
@@ -25,6 +25,12 @@ OUT = os.path.join(HERE, "libpvvote.so")
 EVAL_SRCS = [os.path.join(CSRC, "pveval.hip")]
 EVAL_HDR = os.path.join(REPO, "include", "pveval.h")
 EVAL_OUT = os.path.join(HERE, "libpveval.so")
+# the plain-PnP library (include/pvpose.h), a third library for the same reason; pvepnp_core.h is
+# its kernel's body and belongs to it alone
+POSE_SRCS = [os.path.join(CSRC, "pvepnp.hip")]
+POSE_HDR = os.path.join(REPO, "include", "pvpose.h")
+POSE_OUT = os.path.join(HERE, "libpvpose.so")
+POSE_DEPS = (*POSE_SRCS, os.path.join(CSRC, "pvepnp_core.h"), POSE_HDR)
 ARCH = os.environ.get("PVVOTE_ARCH", "gfx950")
 
 HIPCC_FLAGS = [
@@ -57,17 +63,18 @@ def hipcc() -> str:
 
 def stale(out: str) -> bool:
     """Is `out` missing, or older than any source under csrc/, a public header or this file?
-    For the two libraries the other one's translation units and public header do not count."""
+    For each library the other two's translation units and public headers do not count."""
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    other = {OUT: (*EVAL_SRCS, EVAL_HDR), EVAL_OUT: tuple(SRCS)}.get(out, ())
+    other = {OUT: (*EVAL_SRCS, EVAL_HDR, *POSE_DEPS), EVAL_OUT: (*SRCS, *POSE_DEPS),
+             POSE_OUT: (*SRCS, *EVAL_SRCS, EVAL_HDR)}.get(out, ())
     deps = [os.path.join(CSRC, n) for n in os.listdir(CSRC) if n.endswith((".hip", ".h"))]
-    return any(os.path.getmtime(p) > t for p in (*deps, HDR, EVAL_HDR, __file__) if p not in other)
+    return any(os.path.getmtime(p) > t for p in (*deps, HDR, EVAL_HDR, POSE_HDR, __file__) if p not in other)
 
 
 def needs_build() -> bool:
-    return stale(OUT) or stale(EVAL_OUT)
+    return stale(OUT) or stale(EVAL_OUT) or stale(POSE_OUT)
 
 
 def _link(out: str, srcs, extra=()) -> None:
@@ -80,11 +87,13 @@ def _link(out: str, srcs, extra=()) -> None:
 
 
 def build(force: bool = False, extra=()) -> str:
-    """Build libpvvote.so and libpveval.so (each when stale); returns libpvvote.so's path."""
+    """Build libpvvote.so, libpveval.so and libpvpose.so (each when stale); returns libpvvote.so's path."""
     if force or stale(OUT):
         _link(OUT, SRCS, extra)
     if force or stale(EVAL_OUT):
         _link(EVAL_OUT, EVAL_SRCS, extra)
+    if force or stale(POSE_OUT):
+        _link(POSE_OUT, POSE_SRCS, extra)
     return OUT
 
 

@@ -189,19 +189,26 @@ class Evaluator:
         self.cm_degree_5_recorder.append((m["trans_cm"] < 5.0) & (m["rot_deg"] < 5.0))
         return pose_pred
 
-    def evaluate(self, points_2d, pose_targets, model_id, K):
+    def evaluate(self, points_2d, pose_targets, model_id, K, method="p3p_lm"):
         """Pose from the keypoints alone, then score.  points_2d [b, vn, 2] device tensor,
         pose_targets [b, 3, 4], model_id int [b] or None, K [3, 3] or [b, 3, 3].
 
-        The pose is ``uncertainty_pnp_batch(..., mode="weights")`` at unit weights: P3P on
-        points 0..3, then unweighted Levenberg-Marquardt over all points.  This is not cv2's
-        EPnP, which the reference calls here and which stays out of scope."""
-        from .extend_utils import uncertainty_pnp_batch
+        method "p3p_lm" (the default): ``uncertainty_pnp_batch(..., mode="weights")`` at unit
+        weights, that is P3P on points 0..3, then unweighted Levenberg-Marquardt over all points.
+        method "epnp": EPnP over all points (``pnp_batch``), which is what the reference calls
+        here (cv2's SOLVEPNP_EPNP, EU:19-52); needs vn >= 6.
+        method "epnp_lm": EPnP, then the same Levenberg-Marquardt started from its pose."""
+        from .extend_utils import pnp_batch, uncertainty_pnp_batch
+        if method not in ("p3p_lm", "epnp", "epnp_lm"):
+            raise ValueError(f"unknown method {method!r}: choose from 'p3p_lm', 'epnp', 'epnp_lm'")
         b, vn = int(points_2d.shape[0]), int(points_2d.shape[1])
         mid = self._ids(model_id, b)
-        w = torch.tensor([1.0, 0.0, 1.0], dtype=torch.float64, device=points_2d.device).expand(b, vn, 3)
         p3 = self.points_3d[mid.clamp(0, self.table.nmodels - 1)]
-        Rt = uncertainty_pnp_batch(points_2d, w, p3, K, mode="weights")
+        if method == "p3p_lm":
+            w = torch.tensor([1.0, 0.0, 1.0], dtype=torch.float64, device=points_2d.device).expand(b, vn, 3)
+            Rt = uncertainty_pnp_batch(points_2d, w, p3, K, mode="weights")
+        else:
+            Rt = pnp_batch(points_2d, p3, K, method=method)
         return self._score(Rt, pose_targets, mid, K)
 
     def evaluate_uncertainty(self, mean, cov, pose_targets, model_id, K):

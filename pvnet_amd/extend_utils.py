@@ -144,6 +144,113 @@ def uncertainty_pnp_v2(points_2d, covars, points_3d, camera_matrix, type="single
     return _single(points_2d, covars, points_3d, camera_matrix, "cov_v2")
 
 
+_PNP_METHODS = ("epnp", "epnp_lm")
+# device -> every f64 [n, 3] buffer of rows (1, 0, 1) ever handed out, the largest last.  A captured
+# graph holds a buffer's raw pointer, so none is ever released: a larger request adds a buffer.
+_unit_weights: dict = {}
+
+
+def _unit_w(dev: torch.device, n: int) -> torch.Tensor:
+    bufs = _unit_weights.setdefault(dev, [])
+    if not bufs or bufs[-1].shape[0] < n:
+        bufs.append(torch.tensor([1.0, 0.0, 1.0], dtype=torch.float64, device=dev).repeat(max(n, 1024), 1).contiguous())
+    return bufs[-1][:n]
+
+
+def pnp_batch(points_2d: torch.Tensor, points_3d, camera_matrix, method: str = "epnp",
+              diag: dict | None = None) -> torch.Tensor:
+    """Batched plain PnP on the device: EPnP (``pv_epnp``, include/pvpose.h), the reference's
+    ``pnp()`` (lib/utils/evaluation_utils.py:19-52, cv2's SOLVEPNP_EPNP) for a batch.
+
+    points_2d  [b, pn, 2] device tensor, 6 <= pn <= 64; float64 points are used at full
+               precision, anything else as float32
+    points_3d  f64 [pn, 3] shared, or [b, pn, 3]
+    camera_matrix f64 [3, 3] shared, or [b, 3, 3]
+    method     "epnp": the EPnP pose as cv2's EPNP flag returns it (no refinement);
+               "epnp_lm": EPnP, then the unweighted Levenberg-Marquardt of
+               ``pv_uncertainty_pnp_refine`` at unit weights over all points, started from it
+    diag       optional dict, filled with the device tensors ``status`` i32 [b] (0 ok, 1 degenerate:
+               the pose is then [I | 0]), ``n_used`` i32 [b] and ``cand_err`` f64 [b, 3]; for
+               "epnp_lm" also the refinement's ``iterations``, ``lm_status`` and ``cost``
+    Returns Rt f64 [b, 3, 4] on the inputs' device and current stream.  Nothing is read back and
+    nothing synchronises; after one eager call of the same shape the call can be captured."""
+    from . import _pose_lib
+    if method not in _PNP_METHODS:
+        raise ValueError(f"method must be one of {_PNP_METHODS}")
+    dev = points_2d.device
+    if dev.type != "cuda":
+        raise RuntimeError("points_2d must be a device tensor")
+    if points_2d.dim() != 3 or points_2d.shape[2] != 2:
+        raise RuntimeError("points_2d must be [b, pn, 2]")
+    b, pn = int(points_2d.shape[0]), int(points_2d.shape[1])
+    if not _pose_lib.PV_EPNP_MIN_POINTS <= pn <= _pose_lib.PV_EPNP_MAX_POINTS:
+        raise RuntimeError(f"EPnP needs 6 <= pn <= 64 points per image, got {pn}: with fewer than 6 the null "
+                           "space of its linear system is not unique; use Evaluator.evaluate(method=\"p3p_lm\") "
+                           "or uncertainty_pnp_batch (p3p_lm: P3P, then Levenberg-Marquardt) for 4 or 5 points")
+    p2 = points_2d.contiguous() if points_2d.dtype == torch.float64 else points_2d.to(torch.float32).contiguous()
+    p3 = torch.as_tensor(points_3d, dtype=torch.float64).to(dev).contiguous()
+    K = torch.as_tensor(camera_matrix, dtype=torch.float64).to(dev).contiguous()
+    if tuple(p3.shape) == (pn, 3):
+        p3s = 0
+    elif tuple(p3.shape) == (b, pn, 3):
+        p3s = pn * 3
+    else:
+        raise RuntimeError("points_3d must be [pn, 3] or [b, pn, 3]")
+    if tuple(K.shape) == (3, 3):
+        ks = 0
+    elif tuple(K.shape) == (b, 3, 3):
+        ks = 9
+    else:
+        raise RuntimeError("camera_matrix must be [3, 3] or [b, 3, 3]")
+    f64 = p2.dtype == torch.float64
+    bt = _pose_lib.EpnpBatch(b, pn, None if f64 else p2.data_ptr(), p2.data_ptr() if f64 else None, p3.data_ptr(),
+                             K.data_ptr(), p3s, ks)
+    dg = _pose_lib.EpnpDiag()
+    d = {}
+    if diag is not None:
+        d = dict(status=torch.zeros(b, dtype=torch.int32, device=dev),
+                 n_used=torch.zeros(b, dtype=torch.int32, device=dev),
+                 cand_err=torch.zeros((b, 3), dtype=torch.float64, device=dev))
+        dg = _pose_lib.EpnpDiag(*(d[k].data_ptr() for k in ("status", "n_used", "cand_err")))
+    P = _pose_lib.load()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    out = torch.empty((b, 3, 4), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        if method == "epnp":
+            _pose_lib.check(P.pv_epnp(ctypes.byref(bt), out.data_ptr(), None, ctypes.byref(dg), stream), "pv_epnp")
+        else:
+            L = _lib.load()
+            x0 = torch.empty((b, 6), dtype=torch.float64, device=dev)
+            x1 = torch.empty((b, 6), dtype=torch.float64, device=dev)
+            w = _unit_w(dev, b * pn)
+            _pose_lib.check(P.pv_epnp(ctypes.byref(bt), None, x0.data_ptr(), ctypes.byref(dg), stream), "pv_epnp")
+            lbt = _lib.PnpBatch(b, pn, _lib.PV_PNP_WEIGHTS, None if f64 else p2.data_ptr(), w.data_ptr(),
+                                p3.data_ptr(), K.data_ptr(), p3s, ks, p2.data_ptr() if f64 else None)
+            ldg = _lib.PnpDiag()
+            if diag is not None:
+                d.update(iterations=torch.zeros(b, dtype=torch.int32, device=dev),
+                         lm_status=torch.zeros(b, dtype=torch.int32, device=dev),
+                         cost=torch.zeros(b, dtype=torch.float64, device=dev))
+                ldg = _lib.PnpDiag(None, None, d["iterations"].data_ptr(), d["lm_status"].data_ptr(),
+                                   d["cost"].data_ptr())
+            _lib.check(L.pv_uncertainty_pnp_refine(ctypes.byref(lbt), x0.data_ptr(), x1.data_ptr(),
+                                                   ctypes.byref(ldg), stream), "pv_uncertainty_pnp_refine")
+            _pose_lib.check(P.pv_rt6_to_Rt(x1.data_ptr(), out.data_ptr(), b, stream), "pv_rt6_to_Rt")
+    if diag is not None:
+        diag.update(d)
+    return out
+
+
+def pnp(points_3d, points_2d, camera_matrix, method: str = "epnp"):
+    """The reference's ``evaluation_utils.pnp`` (EU:19-52) in its own argument order: points_3d
+    [pn, 3], points_2d [pn, 2], camera_matrix [3, 3] numpy -> Rt [3, 4] float64, on the current
+    ROCm device (one image of :func:`pnp_batch`)."""
+    dev = _device()
+    p2 = torch.from_numpy(np.ascontiguousarray(points_2d, np.float64)).to(dev)[None]
+    Rt = pnp_batch(p2, np.asarray(points_3d, np.float64), np.asarray(camera_matrix, np.float64), method)
+    return Rt[0].cpu().numpy()
+
+
 def find_nearest_point_idx_batch(ref_pts: torch.Tensor, que_pts: torch.Tensor) -> torch.Tensor:
     """Batched device form of :func:`find_nearest_point_idx`: ref [b, pn1, dim], que [b, pn2, dim]
     (dim 2 or 3) -> int32 [b, pn2], the lowest index of the nearest reference of each query
