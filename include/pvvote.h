@@ -203,8 +203,9 @@ int pv_estimate_voting_distribution(const pv_image_desc *img, const pv_vote_para
 #define PV_PNP_WEIGHTS 0   /* wgt: f64 [pn,3] (wxx, wxy, wyy) per image, as uncertainty_pnp() takes them */
 #define PV_PNP_COV 1       /* wgt: f32 [pn,2,2] covariances -> inv(sqrtm(C)), 0 if C00 < 1e-6 or NaN
                             * (lib/utils/evaluation_utils.py:168-178), then uncertainty_pnp() */
-#define PV_PNP_COV_V2 2    /* wgt: f32 [pn,2,2] -> isotropic 1 / max eig(C), 0 if C00 < 1e-5
-                            * (uncertainty_pnp_v2, extend_utils.py:116-166) */
+#define PV_PNP_COV_V2 2    /* wgt: f32 [pn,2,2] -> isotropic 1 / max eig(C), 0 if C00 < 1e-5 or C00 is NaN
+                            * (a NaN in another entry is a NaN weight; uncertainty_pnp_v2,
+                            * extend_utils.py:116-166) */
 
 typedef struct pv_pnp_batch {
     int32_t b, pn;          /* images; points per image (4 <= pn <= 64) */
@@ -236,8 +237,8 @@ typedef struct pv_pnp_diag {
 #define PV_PNP_STOP_P3P_ONLY 6  /* pn == 4: the P3P pose is the result (extend_utils.py:90-94) */
 
 /* replaces extend_utils.uncertainty_pnp / uncertainty_pnp_v2 (extend_utils.py:63-166): per image the
- * P3P pose of the four highest-weight points (cv2.solvePnP SOLVEPNP_P3P: points 0..2 solve, point 3
- * picks), then the weighted reprojection least squares of src/uncertainty_pnp.cpp:7-92 by Ceres 2.0's
+ * P3P pose of the four highest-weight points (cv2.solvePnP SOLVEPNP_P3P: points 0..2 solve, in their
+ * three cyclic orders pooled, point 3 picks), then the weighted reprojection least squares of src/uncertainty_pnp.cpp:7-92 by Ceres 2.0's
  * Levenberg-Marquardt (restated).  Rt out f64 [b][3][4] = [Rodrigues(r) | t].  One wave per
  * image, fp64. */
 int pv_uncertainty_pnp(const pv_pnp_batch *batch, double *Rt, const pv_pnp_diag *diag, pv_stream_t stream);

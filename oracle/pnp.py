@@ -9,7 +9,7 @@ What it restates (the consumer of the EVD covariances):
 * ``weights_from_cov``   -- lib/utils/evaluation_utils.py:168-178
   (W = inv(sqrtm(C)) per keypoint, zero when C[0,0] < 1e-6 or C has a NaN);
 * ``weights_v2``         -- lib/utils/extend_utils/extend_utils.py:131-139
-  (isotropic 1 / max eigenvalue, zero when C[0,0] < 1e-5);
+  (isotropic 1 / max eigenvalue, zero when C[0,0] < 1e-5 or C[0,0] is NaN);
 * ``uncertainty_pnp``    -- extend_utils.py:63-114: P3P initial pose on the
   four highest-weight points (``cv2.solvePnP(..., SOLVEPNP_P3P)``), then the
   weighted reprojection least squares of
@@ -76,9 +76,9 @@ def weights_v2(cov):
     cov = np.asarray(cov, np.float64)
     w = np.zeros(cov.shape[0], np.float64)
     for i in range(cov.shape[0]):
-        if cov[i, 0, 0] < 1e-5:
-            continue
-        if np.isnan(cov[i]).any():      # the reference's eigvals raises here; the device gives NaN
+        if not cov[i, 0, 0] >= 1e-5:    # a NaN C[0,0] is gated like a small one (the device's rule:
+            continue                    # a zero weight drops the point, a NaN weight poisons the solve)
+        if np.isnan(cov[i]).any():      # a NaN elsewhere: the reference's eigvals raises; both sides give NaN
             w[i] = np.nan
             continue
         w[i] = 1.0 / np.max(np.linalg.eigvals(cov[i]).real)
@@ -123,7 +123,7 @@ def rodrigues_mat_to_vec(R):
 
 
 # ---------------------------------------------------------------- P3P
-def _real_roots4(a):
+def real_roots4(a):
     """Real roots of a4 x^4 + ... + a0 (numpy.roots), each polished by Newton."""
     a = np.asarray(a, np.float64)
     nz = np.nonzero(np.abs(a) > 0)[0]
@@ -146,8 +146,10 @@ def _real_roots4(a):
     return out
 
 
-def p3p_candidates(P, rays):
-    """Grunert's P3P on world points P[0..2] and unit rays[0..2] -> list of (R, t)."""
+def p3p_candidates(P, rays, roots=None):
+    """Grunert's P3P on world points P[0..2] and unit rays[0..2] -> list of (R, t).
+    ``roots`` replaces the quartic's root finder (tests run the device's one here)."""
+    roots = roots or real_roots4
     P = np.asarray(P, np.float64)
     j = np.asarray(rays, np.float64)
     a = np.linalg.norm(P[1] - P[2])
@@ -165,7 +167,7 @@ def p3p_candidates(P, rays):
     A1 = 4 * (-amc * (1 + amc) * cb + 2 * a2 / b2 * cg ** 2 * cb - (1 - apc) * ca * cg)
     A0 = (1 + amc) ** 2 - 4 * a2 / b2 * cg ** 2
     out = []
-    for v in _real_roots4([A4, A3, A2, A1, A0]):
+    for v in roots([A4, A3, A2, A1, A0]):
         if v <= 0:
             continue
         den = 2 * (cg - v * ca)
@@ -204,10 +206,20 @@ def _frames_pose(P, C):
     return R, t
 
 
-def p3p_pose(P4, x4, K):
+P3P_ORDERS = ((0, 1, 2), (1, 2, 0), (2, 0, 1))
+
+
+def p3p_pose(P4, x4, K, roots=None, orders=P3P_ORDERS):
     """cv2.solvePnP(P4, x4, K, 0, flags=SOLVEPNP_P3P): candidates from points
     0..2, the one reprojecting point 3 closest (squared pixels) wins.
-    Returns (ok, rvec, t)."""
+
+    The candidate set does not depend on which of the three points plays
+    which role in Grunert's elimination, but its conditioning does: seen
+    face-on (a box face parallel to the image plane) ``den = 2 (cg - v ca)``
+    vanishes with its numerator and the true solution is a double root in
+    ``v``.  So the candidates of the three cyclic orders are pooled, in this
+    fixed order, and the strictly smaller error of point 3 wins (DESIGN.md
+    10a).  ``orders=((0, 1, 2),)`` is the single solve.  Returns (ok, rvec, t)."""
     P4 = np.asarray(P4, np.float64)
     x4 = np.asarray(x4, np.float64)
     fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
@@ -216,13 +228,15 @@ def p3p_pose(P4, x4, K):
     rays = np.stack([mu, mv, np.ones(4)], 1)
     rays /= np.linalg.norm(rays, axis=1, keepdims=True)
     best, best_e = None, None
-    for R, t in p3p_candidates(P4[:3], rays[:3]):
-        X = R @ P4[3] + t
-        if X[2] == 0:
-            continue
-        e = (cx + fx * X[0] / X[2] - x4[3, 0]) ** 2 + (cy + fy * X[1] / X[2] - x4[3, 1]) ** 2
-        if best is None or e < best_e:
-            best, best_e = (R, t), e
+    for o in orders:
+        o = list(o)
+        for R, t in p3p_candidates(P4[o], rays[o], roots):
+            X = R @ P4[3] + t
+            if X[2] == 0:
+                continue
+            e = (cx + fx * X[0] / X[2] - x4[3, 0]) ** 2 + (cy + fy * X[1] / X[2] - x4[3, 1]) ** 2
+            if best is None or e < best_e:
+                best, best_e = (R, t), e
     if best is None:
         return False, np.zeros(3), np.zeros(3)
     return True, rodrigues_mat_to_vec(best[0]), best[1]
@@ -323,14 +337,35 @@ def _evaluate(x, pts2d, pts3d, wgt, K, jac):
 
 
 # ---------------------------------------------------------------- Ceres 2.0 LM (restated)
+def _rel(value, threshold):
+    """Relative distance of a tested quantity from its threshold."""
+    with np.errstate(over="ignore"):
+        return abs(value - threshold) / threshold
+
+
 def ceres_lm(x0, pts2d, pts3d, wgt, K, max_iter=50, diag=None):
     """TrustRegionMinimizer + LevenbergMarquardtStrategy with the default
-    Solver::Options (see the module docstring); returns the final x (6)."""
+    Solver::Options (see the module docstring); returns the final x (6).
+
+    ``diag`` receives ``iterations``, ``cost``, ``status`` and, for the tests
+    that demand the device take the same path:
+
+    * ``trace``: one dict per iteration -- ``chol_ok``, ``accepted``,
+      ``cand_finite`` (the candidate's cost; None when it was never evaluated),
+      ``radius`` (after the iteration's update), ``grew`` (the radius rose) and
+      ``h_max`` (the largest diagonal entry of the unscaled J^T J, which the
+      device forms and this function does not);
+    * ``margin``: the smallest relative distance |value - threshold| / threshold
+      over every threshold comparison taken on the way (gradient, parameter and
+      function tolerances, ``rho`` against the minimum relative decrease, the
+      radius against its minimum, a finite candidate cost against overflow).  A run whose margin is far above the two
+      sides' rounding differences takes the same decisions on both."""
     x = np.array(x0, np.float64)
     cost, r, J = evaluate(x, pts2d, pts3d, wgt, K)
+    trace, margin = [], np.inf
     if not np.isfinite(cost):            # (e.g. the zero pose after a failed P3P): nothing to minimise
         if diag is not None:
-            diag.update(iterations=0, cost=cost, status="max_iterations")
+            diag.update(iterations=0, cost=cost, status="max_iterations", trace=trace, margin=margin)
         return x
     scale = 1.0 / (1.0 + np.sqrt((J * J).sum(0)))          # jacobi scaling, fixed at iteration 0
     radius, decrease = 1e4, 2.0
@@ -338,12 +373,17 @@ def ceres_lm(x0, pts2d, pts3d, wgt, K, max_iter=50, diag=None):
     status = "max_iterations"
     while True:
         g = J.T @ r
+        margin = min(margin, _rel(np.max(np.abs(g)), 1e-10))
         if np.max(np.abs(g)) <= 1e-10:
             status = "gradient"
             break
         if it >= max_iter:
             break
         it += 1
+        with np.errstate(over="ignore"):
+            h_max = float((J * J).sum(0).max())
+        rec = dict(chol_ok=True, accepted=False, cand_finite=None, radius=radius, grew=False, h_max=h_max)
+        trace.append(rec)
         Js = J * scale
         d = np.clip((Js * Js).sum(0), 1e-6, 1e32)
         A = Js.T @ Js + np.diag(d / radius)
@@ -354,8 +394,11 @@ def ceres_lm(x0, pts2d, pts3d, wgt, K, max_iter=50, diag=None):
         except np.linalg.LinAlgError:
             ok = False
         if not ok:
+            rec["chol_ok"] = False
             radius /= decrease
             decrease *= 2.0
+            rec["radius"] = radius
+            margin = min(margin, _rel(radius, 1e-32))
             if radius < 1e-32:
                 status = "radius"
                 break
@@ -363,28 +406,38 @@ def ceres_lm(x0, pts2d, pts3d, wgt, K, max_iter=50, diag=None):
         mr = Js @ step
         model_change = -float(mr @ (r + mr / 2.0))
         delta = step * scale
-        if np.linalg.norm(delta) <= 1e-8 * (np.linalg.norm(x) + 1e-8):
+        ptol = 1e-8 * (np.linalg.norm(x) + 1e-8)
+        margin = min(margin, _rel(np.linalg.norm(delta), ptol))
+        if np.linalg.norm(delta) <= ptol:
             status = "parameter"
             break
         xc = x + delta
         cc, rc, _ = evaluate(xc, pts2d, pts3d, wgt, K, jac=False)
+        rec["cand_finite"] = bool(np.isfinite(cc))
+        if np.isfinite(cc):     # (2 cc = r^T r is what overflows)
+            margin = min(margin, _rel(abs(cost - cc), 1e-6 * cost), _rel(cc, 0.5 * np.finfo(np.float64).max))
         if np.isfinite(cc) and abs(cost - cc) <= 1e-6 * cost:
             status = "function"
             break
         rho = (cost - cc) / model_change if (np.isfinite(cc) and model_change > 0) else -np.inf
+        margin = min(margin, _rel(rho, 1e-3))
         if rho > 1e-3:
             x = xc
             cost, r, J = evaluate(x, pts2d, pts3d, wgt, K)
-            radius = min(1e16, radius / max(1.0 / 3.0, 1.0 - (2.0 * rho - 1.0) ** 3))
+            new_radius = min(1e16, radius / max(1.0 / 3.0, 1.0 - (2.0 * rho - 1.0) ** 3))
+            rec.update(accepted=True, grew=new_radius > radius, radius=new_radius)
+            radius = new_radius
             decrease = 2.0
         else:
             radius /= decrease
             decrease *= 2.0
+            rec["radius"] = radius
+            margin = min(margin, _rel(radius, 1e-32))
             if radius < 1e-32:
                 status = "radius"
                 break
     if diag is not None:
-        diag.update(iterations=it, cost=cost, status=status)
+        diag.update(iterations=it, cost=cost, status=status, trace=trace, margin=margin)
     return x
 
 

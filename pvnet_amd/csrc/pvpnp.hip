@@ -16,7 +16,8 @@
 // Ceres' AutoDiffCostFunction evaluates them); J^T J, J^T r and the cost are
 // column sums over the lanes through LDS; the 6x6 trust-region solve runs
 // redundantly in every lane (uniform values, no divergence).  All fp64, as the
-// reference.  The P3P initial pose runs in lane 0 (a few hundred flops).
+// reference.  The P3P initial pose runs in lanes 0..2, one order of its solving
+// points each (a few hundred flops).
 #include <hip/hip_runtime.h>
 
 #include <float.h>
@@ -175,7 +176,8 @@ __device__ __forceinline__ void weights_from_cov(const float *c4, int mode, doub
         w[1] = -b / det;
         w[2] = a / det;
     } else {
-        // 1 / max eigenvalue of the symmetric 2x2
+        // 1 / max eigenvalue of the symmetric 2x2; a NaN c00 is gated like a small one (zero weight:
+        // the point drops out), a NaN in another entry gives a NaN weight
         if (!(c00 >= 1e-5)) return;
         const double m = 0.5 * (c00 + c11), q = sqrt(0.25 * (c00 - c11) * (c00 - c11) + c01 * c10);
         const double lam = m + q;
@@ -328,27 +330,20 @@ __device__ int quartic_real_roots(const double a[5], double out[4]) {
 }
 
 // ---------------------------------------------------------------- P3P (cv2 SOLVEPNP_P3P restated)
-// World points P[4], image points x[4] (pixels): candidates from points
-// 0..2 (Grunert's quartic, Haralick et al. 1994), the one reprojecting point 3
-// closest wins.  Returns false if there is no candidate.
-__device__ bool p3p_pose(const double P[4][3], const double x[4][2], const Cam &cam, double rvec[3],
-                         double t[3]) {
-    double j[4][3];
-    for (int i = 0; i < 4; ++i) {
-        const double mu = (x[i][0] - cam.px) / cam.fx, mv = (x[i][1] - cam.py) / cam.fy;
-        const double nn = sqrt(mu * mu + mv * mv + 1.0);
-        j[i][0] = mu / nn;
-        j[i][1] = mv / nn;
-        j[i][2] = 1.0 / nn;
-    }
+// The candidates of one order of the three solving points: Q[0..2] world points,
+// j[0..2] their unit rays (Grunert's quartic, Haralick et al. 1994).  Each
+// candidate pose is scored by its reprojection of the fourth point (P3, x3); a
+// strictly smaller error than *best replaces rvec / t.
+__device__ void p3p_order(const double Q[3][3], const double j[3][3], const double P3[3], const double x3[2],
+                          const Cam &cam, bool *found, double *best, double rvec[3], double t[3]) {
     double d12[3], d02[3], d01[3];
     for (int k = 0; k < 3; ++k) {
-        d12[k] = P[1][k] - P[2][k];
-        d02[k] = P[0][k] - P[2][k];
-        d01[k] = P[0][k] - P[1][k];
+        d12[k] = Q[1][k] - Q[2][k];
+        d02[k] = Q[0][k] - Q[2][k];
+        d01[k] = Q[0][k] - Q[1][k];
     }
     const double a2 = dot3(d12, d12), b2 = dot3(d02, d02), c2 = dot3(d01, d01);
-    if (b2 == 0.0) return false;
+    if (b2 == 0.0) return;
     const double ca = dot3(j[1], j[2]), cb = dot3(j[0], j[2]), cg = dot3(j[0], j[1]);
     const double amc = (a2 - c2) / b2, apc = (a2 + c2) / b2;
     double A[5];
@@ -361,10 +356,7 @@ __device__ bool p3p_pose(const double P[4][3], const double x[4][2], const Cam &
     double roots[4];
     const int nr = quartic_real_roots(A, roots);
     double FP[3][3];
-    const double P3[3][3] = {{P[0][0], P[0][1], P[0][2]}, {P[1][0], P[1][1], P[1][2]}, {P[2][0], P[2][1], P[2][2]}};
-    if (!tri_frame(P3, FP)) return false;
-    bool found = false;
-    double best = 0.0;
+    if (!tri_frame(Q, FP)) return;
     for (int k = 0; k < nr; ++k) {
         const double v = roots[k];
         if (!(v > 0.0)) continue;
@@ -386,23 +378,46 @@ __device__ bool p3p_pose(const double P[4][3], const double x[4][2], const Cam &
         for (int r = 0; r < 3; ++r)
             for (int c = 0; c < 3; ++c) R[r][c] = FC[r][0] * FP[c][0] + FC[r][1] * FP[c][1] + FC[r][2] * FP[c][2];
         double tt[3];
-        for (int r = 0; r < 3; ++r) tt[r] = C[0][r] - (R[r][0] * P[0][0] + R[r][1] * P[0][1] + R[r][2] * P[0][2]);
+        for (int r = 0; r < 3; ++r) tt[r] = C[0][r] - (R[r][0] * Q[0][0] + R[r][1] * Q[0][1] + R[r][2] * Q[0][2]);
         double X[3];
-        for (int r = 0; r < 3; ++r) X[r] = R[r][0] * P[3][0] + R[r][1] * P[3][1] + R[r][2] * P[3][2] + tt[r];
+        for (int r = 0; r < 3; ++r) X[r] = R[r][0] * P3[0] + R[r][1] * P3[1] + R[r][2] * P3[2] + tt[r];
         if (X[2] == 0.0) continue;
-        const double ex = cam.px + cam.fx * X[0] / X[2] - x[3][0], ey = cam.py + cam.fy * X[1] / X[2] - x[3][1];
+        const double ex = cam.px + cam.fx * X[0] / X[2] - x3[0], ey = cam.py + cam.fy * X[1] / X[2] - x3[1];
         const double e = ex * ex + ey * ey;
-        if (!found || e < best) {
-            found = true;
-            best = e;
+        if (!*found || e < *best) {
+            *found = true;
+            *best = e;
             rodrigues_to_vec(R, rvec);
             for (int r = 0; r < 3; ++r) t[r] = tt[r];
         }
     }
-    if (!found) {
-        rvec[0] = rvec[1] = rvec[2] = 0.0;
-        t[0] = t[1] = t[2] = 0.0;
+}
+
+// World points P[4], image points x[4] (pixels): candidates from points 0..2,
+// the one reprojecting point 3 closest wins.  The candidate set does not depend
+// on which of the three points plays which role in the elimination, but its
+// conditioning does: seen face-on, den = 2 (cg - v ca) vanishes with its
+// numerator and the true solution is a double root in v that the root finder
+// loses or gets to sqrt(eps).  So the candidates of the three cyclic orders
+// (0,1,2), (1,2,0), (2,0,1) are pooled, in that order (the oracle
+// does the same).  This is order o's share: its best candidate (the first of
+// equals), false if it has none; the kernel merges the three in order, a
+// strictly smaller error winning, which is the pooled pick.
+__device__ bool p3p_pose_order(const double P[4][3], const double x[4][2], const Cam &cam, int o, double *best,
+                               double rvec[3], double t[3]) {
+    double Q[3][3], jo[3][3];
+    for (int i = 0; i < 3; ++i) {
+        const int s = (o + i) % 3;
+        const double mu = (x[s][0] - cam.px) / cam.fx, mv = (x[s][1] - cam.py) / cam.fy;
+        const double nn = sqrt(mu * mu + mv * mv + 1.0);
+        jo[i][0] = mu / nn;
+        jo[i][1] = mv / nn;
+        jo[i][2] = 1.0 / nn;
+        for (int k = 0; k < 3; ++k) Q[i][k] = P[s][k];
     }
+    bool found = false;
+    *best = 0.0;
+    p3p_order(Q, jo, P[3], x[3], cam, &found, best, rvec, t);
     return found;
 }
 
@@ -413,6 +428,8 @@ struct Shared {
     double cost_part[kMaxPts];
     double cost;
     double x0[6];                      // initial pose (lane 0 -> all)
+    double cand[3][7];                 // P3P: order o's best candidate (error, rvec, t), lanes 0..2
+    int cand_ok[3];
     int ok;
     int sel[4];
 };
@@ -628,7 +645,7 @@ __global__ __launch_bounds__(64) void k_uncertainty_pnp(pv_pnp_batch bt, const d
             if (pos >= pn - 4) S.sel[pos - (pn - 4)] = lane;
         }
         __syncthreads();
-        if (lane == 0) {
+        if (lane < 3) {   // one cyclic order of the solving points per lane
             double P[4][3], xx[4][2];
             for (int k = 0; k < 4; ++k) {
                 const int s = S.sel[k];
@@ -637,9 +654,18 @@ __global__ __launch_bounds__(64) void k_uncertainty_pnp(pv_pnp_batch bt, const d
                 xx[k][0] = bt.pts2d64 ? bt.pts2d64[o] : (double)bt.pts2d[o];
                 xx[k][1] = bt.pts2d64 ? bt.pts2d64[o + 1] : (double)bt.pts2d[o + 1];
             }
-            double rv[3], tt[3];
-            S.ok = p3p_pose(P, xx, cam, rv, tt) ? 1 : 0;
-            for (int k = 0; k < 3; ++k) { S.x0[k] = rv[k]; S.x0[3 + k] = tt[k]; }
+            double e, rv[3] = {}, tt[3] = {};
+            S.cand_ok[lane] = p3p_pose_order(P, xx, cam, lane, &e, rv, tt) ? 1 : 0;
+            S.cand[lane][0] = e;
+            for (int k = 0; k < 3; ++k) { S.cand[lane][1 + k] = rv[k]; S.cand[lane][4 + k] = tt[k]; }
+        }
+        __syncthreads();
+        if (lane == 0) {
+            int win = -1;
+            for (int o = 0; o < 3; ++o)
+                if (S.cand_ok[o] && (win < 0 || S.cand[o][0] < S.cand[win][0])) win = o;
+            S.ok = win >= 0 ? 1 : 0;
+            for (int k = 0; k < 6; ++k) S.x0[k] = win >= 0 ? S.cand[win][1 + k] : 0.0;
         }
         __syncthreads();
         for (int k = 0; k < 6; ++k) x[k] = S.x0[k];

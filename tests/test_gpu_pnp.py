@@ -60,27 +60,27 @@ def _batch(seeds, pn=9):
 
 @pytest.mark.parametrize("mode", ["cov", "cov_v2"])
 def test_full_pnp_matches_oracle(mode, device, eu):
-    p2, cov, p3, cases = _batch(range(64))
-    cov[3, 2] = np.float32(1e-7) * np.eye(2, dtype=np.float32)     # gated -> zero weight
-    cov[5, 4, 1, 0] = np.nan                                          # NaN -> zero weight (mode cov)
-    if mode == "cov_v2":
-        cov[5, 4, 1, 0] = 0.0
+    """64 noisy images with a gated and a NaN covariance (tests/pnp_cases.py full_batch): the
+    start, the pose, and the LM's path -- iterations, stop state and final cost; the oracle's
+    decisions sit at a relative margin >= 1e-6 from their thresholds (tests/test_pnp_cases.py)."""
+    from tests import pnp_cases as C
+    p2, cov, p3, refs = C.full_batch(mode)
     diag = {}
     Rt = eu.uncertainty_pnp_batch(torch.from_numpy(p2).to(device), torch.from_numpy(cov).to(device), p3, K_LM,
                                   mode=mode, diag=diag).cpu().numpy()
-    for i in range(len(cases)):
-        d = {}
-        if mode == "cov":
-            ref = P.uncertainty_pnp(p2[i], P.weights_from_cov(cov[i]), p3, K_LM, diag=d)
-        else:
-            ref = P.uncertainty_pnp_v2(p2[i], cov[i], p3, K_LM, diag=d)
-        np.testing.assert_allclose(diag["init_rt"][i].cpu().numpy(), d["init"], atol=1e-6, err_msg=f"init {i}")
-        assert bool(diag["p3p_ok"][i]) == bool(d["p3p_ok"])
+    dg = {k: v.cpu().numpy() for k, v in diag.items()}
+    assert len(refs) == 64
+    for i, (ref, d) in enumerate(refs):
+        np.testing.assert_allclose(dg["init_rt"][i], d["init"], atol=1e-6, err_msg=f"init {i}")
+        assert bool(dg["p3p_ok"][i]) == bool(d["p3p_ok"])
         # (no P3P solution: the reference's cv2 path has no pose to start from;
         # both sides then start from zero and may end non-finite alike)
         np.testing.assert_allclose(Rt[i], ref, atol=TOL, err_msg=f"image {i}", equal_nan=True)
-    assert (diag["status"].cpu().numpy() > 0).all()
-    assert diag["p3p_ok"].cpu().numpy().mean() > 0.9
+        assert dg["iterations"][i] == d["iterations"], f"image {i}"
+        assert dg["status"][i] == C.STOP[d["status"]], f"image {i}"
+        np.testing.assert_allclose(dg["cost"][i], d["cost"], rtol=1e-9, atol=0, err_msg=f"image {i}", equal_nan=True)
+    assert (dg["status"] > 0).all()
+    assert dg["p3p_ok"].mean() > 0.9
 
 
 def test_numpy_api_matches_batch_and_reference_signature(device, eu):
