@@ -1,4 +1,4 @@
-"""Build libpvvote.so, libpveval.so and libpvpose.so (the HIP C-ABI libraries) in-tree for gfx950.
+"""Build libpvvote.so, libpveval.so, libpvpose.so and libpvrender.so (the HIP C-ABI libraries) in-tree for gfx950.
 
     python -m pvnet_amd.build            # or __graft_entry__.build()
 
@@ -31,6 +31,12 @@ POSE_SRCS = [os.path.join(CSRC, "pvepnp.hip")]
 POSE_HDR = os.path.join(REPO, "include", "pvpose.h")
 POSE_OUT = os.path.join(HERE, "libpvpose.so")
 POSE_DEPS = (*POSE_SRCS, os.path.join(CSRC, "pvepnp_core.h"), POSE_HDR)
+# the render library (include/pvrender.h), a fourth for the same reason; its one translation unit
+# includes no other file of csrc/
+RENDER_SRCS = [os.path.join(CSRC, "pvrender.hip")]
+RENDER_HDR = os.path.join(REPO, "include", "pvrender.h")
+RENDER_OUT = os.path.join(HERE, "libpvrender.so")
+RENDER_DEPS = (*RENDER_SRCS, RENDER_HDR)
 ARCH = os.environ.get("PVVOTE_ARCH", "gfx950")
 
 HIPCC_FLAGS = [
@@ -63,18 +69,22 @@ def hipcc() -> str:
 
 def stale(out: str) -> bool:
     """Is `out` missing, or older than any source under csrc/, a public header or this file?
-    For each library the other two's translation units and public headers do not count."""
+    For each library the other three's translation units and public headers do not count, and
+    libpvrender.so, which includes nothing else of csrc/, depends on its own sources alone."""
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    other = {OUT: (*EVAL_SRCS, EVAL_HDR, *POSE_DEPS), EVAL_OUT: (*SRCS, *POSE_DEPS),
-             POSE_OUT: (*SRCS, *EVAL_SRCS, EVAL_HDR)}.get(out, ())
+    if out == RENDER_OUT:
+        return any(os.path.getmtime(p) > t for p in (*RENDER_DEPS, __file__))
+    other = {OUT: (*EVAL_SRCS, EVAL_HDR, *POSE_DEPS, *RENDER_DEPS), EVAL_OUT: (*SRCS, *POSE_DEPS, *RENDER_DEPS),
+             POSE_OUT: (*SRCS, *EVAL_SRCS, EVAL_HDR, *RENDER_DEPS)}.get(out, ())
     deps = [os.path.join(CSRC, n) for n in os.listdir(CSRC) if n.endswith((".hip", ".h"))]
-    return any(os.path.getmtime(p) > t for p in (*deps, HDR, EVAL_HDR, POSE_HDR, __file__) if p not in other)
+    return any(os.path.getmtime(p) > t for p in (*deps, HDR, EVAL_HDR, POSE_HDR, RENDER_HDR, __file__)
+               if p not in other)
 
 
 def needs_build() -> bool:
-    return stale(OUT) or stale(EVAL_OUT) or stale(POSE_OUT)
+    return stale(OUT) or stale(EVAL_OUT) or stale(POSE_OUT) or stale(RENDER_OUT)
 
 
 def _link(out: str, srcs, extra=()) -> None:
@@ -87,13 +97,16 @@ def _link(out: str, srcs, extra=()) -> None:
 
 
 def build(force: bool = False, extra=()) -> str:
-    """Build libpvvote.so, libpveval.so and libpvpose.so (each when stale); returns libpvvote.so's path."""
+    """Build libpvvote.so, libpveval.so, libpvpose.so and libpvrender.so (each when stale); returns
+    libpvvote.so's path."""
     if force or stale(OUT):
         _link(OUT, SRCS, extra)
     if force or stale(EVAL_OUT):
         _link(EVAL_OUT, EVAL_SRCS, extra)
     if force or stale(POSE_OUT):
         _link(POSE_OUT, POSE_SRCS, extra)
+    if force or stale(RENDER_OUT):
+        _link(RENDER_OUT, RENDER_SRCS, extra)
     return OUT
 
 
