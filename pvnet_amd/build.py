@@ -1,4 +1,5 @@
-"""Build libpvvote.so, libpveval.so, libpvpose.so and libpvrender.so (the HIP C-ABI libraries) in-tree for gfx950.
+"""Build libpvvote.so, libpveval.so, libpvpose.so, libpvrender.so and libpvmodel.so (the HIP C-ABI libraries) in-tree
+for gfx950.
 
     python -m pvnet_amd.build            # or __graft_entry__.build()
 
@@ -37,6 +38,12 @@ RENDER_SRCS = [os.path.join(CSRC, "pvrender.hip")]
 RENDER_HDR = os.path.join(REPO, "include", "pvrender.h")
 RENDER_OUT = os.path.join(HERE, "libpvrender.so")
 RENDER_DEPS = (*RENDER_SRCS, RENDER_HDR)
+# the model-preparation library (include/pvmodel.h), a fifth; like the render library its one
+# translation unit includes no other file of csrc/
+MODEL_SRCS = [os.path.join(CSRC, "pvmodel.hip")]
+MODEL_HDR = os.path.join(REPO, "include", "pvmodel.h")
+MODEL_OUT = os.path.join(HERE, "libpvmodel.so")
+MODEL_DEPS = (*MODEL_SRCS, MODEL_HDR)
 ARCH = os.environ.get("PVVOTE_ARCH", "gfx950")
 
 HIPCC_FLAGS = [
@@ -69,22 +76,25 @@ def hipcc() -> str:
 
 def stale(out: str) -> bool:
     """Is `out` missing, or older than any source under csrc/, a public header or this file?
-    For each library the other three's translation units and public headers do not count, and
-    libpvrender.so, which includes nothing else of csrc/, depends on its own sources alone."""
+    For each library the other four's translation units and public headers do not count, and
+    libpvrender.so and libpvmodel.so, which include nothing else of csrc/, depend on their own
+    sources alone."""
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    if out == RENDER_OUT:
-        return any(os.path.getmtime(p) > t for p in (*RENDER_DEPS, __file__))
-    other = {OUT: (*EVAL_SRCS, EVAL_HDR, *POSE_DEPS, *RENDER_DEPS), EVAL_OUT: (*SRCS, *POSE_DEPS, *RENDER_DEPS),
-             POSE_OUT: (*SRCS, *EVAL_SRCS, EVAL_HDR, *RENDER_DEPS)}.get(out, ())
+    own = {RENDER_OUT: RENDER_DEPS, MODEL_OUT: MODEL_DEPS}.get(out)
+    if own is not None:
+        return any(os.path.getmtime(p) > t for p in (*own, __file__))
+    other = {OUT: (*EVAL_SRCS, EVAL_HDR, *POSE_DEPS, *RENDER_DEPS, *MODEL_DEPS),
+             EVAL_OUT: (*SRCS, *POSE_DEPS, *RENDER_DEPS, *MODEL_DEPS),
+             POSE_OUT: (*SRCS, *EVAL_SRCS, EVAL_HDR, *RENDER_DEPS, *MODEL_DEPS)}.get(out, ())
     deps = [os.path.join(CSRC, n) for n in os.listdir(CSRC) if n.endswith((".hip", ".h"))]
     return any(os.path.getmtime(p) > t for p in (*deps, HDR, EVAL_HDR, POSE_HDR, RENDER_HDR, __file__)
                if p not in other)
 
 
 def needs_build() -> bool:
-    return stale(OUT) or stale(EVAL_OUT) or stale(POSE_OUT) or stale(RENDER_OUT)
+    return stale(OUT) or stale(EVAL_OUT) or stale(POSE_OUT) or stale(RENDER_OUT) or stale(MODEL_OUT)
 
 
 def _link(out: str, srcs, extra=()) -> None:
@@ -97,8 +107,8 @@ def _link(out: str, srcs, extra=()) -> None:
 
 
 def build(force: bool = False, extra=()) -> str:
-    """Build libpvvote.so, libpveval.so, libpvpose.so and libpvrender.so (each when stale); returns
-    libpvvote.so's path."""
+    """Build libpvvote.so, libpveval.so, libpvpose.so, libpvrender.so and libpvmodel.so (each when
+    stale); returns libpvvote.so's path."""
     if force or stale(OUT):
         _link(OUT, SRCS, extra)
     if force or stale(EVAL_OUT):
@@ -107,6 +117,8 @@ def build(force: bool = False, extra=()) -> str:
         _link(POSE_OUT, POSE_SRCS, extra)
     if force or stale(RENDER_OUT):
         _link(RENDER_OUT, RENDER_SRCS, extra)
+    if force or stale(MODEL_OUT):
+        _link(MODEL_OUT, MODEL_SRCS, extra)
     return OUT
 
 

@@ -67,6 +67,32 @@ class ModelTable:
         self.diameter = torch.tensor([float(d) for _, d, _ in models], dtype=torch.float64).to(device)
         self.symmetric = torch.tensor([bool(s) for _, _, s in models], dtype=torch.bool).to(device)
 
+    @classmethod
+    def from_meshes(cls, mesh_table, symmetric=False):
+        """The table of a :class:`~pvnet_amd.render.MeshTable`'s models: ``points`` and ``offsets`` are
+        the mesh table's own vertex tensors (not copies), and ``diameter`` is computed on the device
+        (``pvnet_amd.models.diameter``), so nothing is brought from the host.
+
+        symmetric  a bool for every model, or a sequence of one bool per model"""
+        from . import models
+        n = int(mesh_table.nmodels)
+        sym = [bool(symmetric)] * n if isinstance(symmetric, (bool, int)) else [bool(s) for s in symmetric]
+        if len(sym) != n:
+            raise ValueError("symmetric must be a bool or one bool per model")
+        self = cls.__new__(cls)
+        self.device = mesh_table.device
+        self.nmodels = n
+        self.total = int(mesh_table.total_v)
+        self.max_pn = int(mesh_table.max_verts)
+        self.counts = tuple(int(c) for c in mesh_table.vert_counts)
+        self.any_symmetric = any(sym)
+        self.all_symmetric = all(sym)
+        self.points = mesh_table.verts
+        self.offsets = mesh_table.vert_off
+        self.diameter = models.diameter(mesh_table)
+        self.symmetric = torch.tensor(sym, dtype=torch.bool).to(self.device)
+        return self
+
 
 def _metric_bits(metrics) -> int:
     bits = 0
