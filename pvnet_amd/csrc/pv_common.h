@@ -40,6 +40,17 @@ constexpr int kRefineLdsHyp = 1024;          // hypotheses per keypoint kept in 
 constexpr float kHypMax = 1.0e17f;           // |hx|,|hy| above -> exact-only hypothesis
 constexpr float kLattice = 2.5e-6f;          // |h - round(h)| below (both axes) -> exact-only
 constexpr float kN1Max = 1.0e18f;            // |direction| above -> exact-only pixel
+// The two norm1 tests of a pixel on its squared norm s (fl(fl(nx nx) + fl(ny ny)),
+// the reference's own sum): the correctly rounded sqrtf is monotone, so
+// sqrtf(s) <= c holds exactly for s <= T with T the largest float whose root
+// rounds to <= c.  c = 1e-6f = 0x1.0c6f7ap-20: c^2 = 0x1.19799812...p-40; T =
+// 0x1.19799ap-40 has sqrtf(T) = c and its successor's root is c's successor.
+// c = 1e18f = 0x1.bc16d6p+59: c^2 = 0x1.812f9b7d...p+119; T = 0x1.812f9cp+119
+// likewise.  NaN fails both forms; +inf and every s above T fail both, a
+// subnormal or zero s passes both.  tests/test_norm_constants.py checks the
+// equivalence around both constants and over the whole positive range.
+constexpr float kN1SqLow = 0x1.19799ap-40f;  // sqrtf(s) <= 1e-6f   <=>  s <= kN1SqLow
+constexpr float kN1SqMax = 0x1.812f9cp+119f; // sqrtf(s) <= kN1Max  <=>  s <= kN1SqMax
 
 __host__ __device__ inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 

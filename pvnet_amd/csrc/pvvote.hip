@@ -208,10 +208,12 @@ __device__ __forceinline__ float4 prep_pixel(float cx, float cy, float nx, float
 // the direction rounded per component after scaling by rsq (the fast test
 // needs only its direction); *exo: votes, but outside the fast domain
 __device__ __forceinline__ float4 prep_compacted(const F4 &e, bool *exo) {
-    const float n1 = sqrtf(e.z * e.z + e.w * e.w);
-    const bool valid = !below_1e6(n1);
+    // norm1 = sqrtf(s) is only compared here, and sqrtf is monotone: the two
+    // tests are made on s against kN1SqLow / kN1SqMax (pv_common.h), no root
+    const float s = e.z * e.z + e.w * e.w;
+    const bool valid = !(s <= kN1SqLow);
     const float rs = __builtin_amdgcn_rsqf(fmaf(e.z, e.z, e.w * e.w));
-    *exo = valid && !(n1 <= kN1Max);
+    *exo = valid && !(s <= kN1SqMax);
     return make_float4(valid ? e.x : __builtin_nanf(""), e.y, e.z * rs, e.w * rs);
 }
 
@@ -884,8 +886,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
         };
         load_px(ts, min(kMChunk, te - ts));
         // hypotheses: lane makes h = hg*128 + i*64 + lane (i = 0, 1), stored at
-        // [set 2i + half][col] -- the same linear index
-        uint32_t hfm = 0, hxm = 0;              // per set: fast / exact-only (bit j)
+        // [set 2i + half][col] -- the same linear index.  The making lane also
+        // classifies it (fast / exact-only), once per hypothesis: bit i and bit
+        // 2 + i of `own` are set 2i + half's two classes of column col, and one
+        // v_permlane32_swap gives every lane both halves' words, i.e. all four
+        // sets' classes of its column (the same predicate on the same value as
+        // a classification of the four sets in every lane)
+        uint32_t own = 0;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int h = hg * kGroup + i * kWave + lane;
@@ -894,20 +901,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
             const float2 hv = a.hyp ? item_hyp<false, PREPPED>(a, b, v, h, hl, n, false)
                                     : item_hyp<PREPPED, PREPPED>(a, b, v, h, hl, n, PREPPED && ts == 0);
             hlds[i * kWave + lane] = hv;
+            const bool fin = isfinite(hv.x) && isfinite(hv.y);
+            const bool xo = hl && fin &&
+                            (hyp_exact_only(hv.x, hv.y) || !(fabsf(hv.x) < kMHypMax && fabsf(hv.y) < kMHypMax));
+            own |= (hl && fin && !xo) ? 1u << i : 0u;
+            own |= xo ? 4u << i : 0u;
         }
         __builtin_amdgcn_wave_barrier();
         // (the exact hypotheses stay in LDS, hlds[set * 32 + col]: read where
         // needed rather than held in registers across the hot loop)
-#pragma unroll
-        for (int j = 0; j < kMSet; ++j) {
-            const int h = hg * kGroup + j * 32 + col;
-            const float2 hv = hlds[j * 32 + col];
-            const bool fin = isfinite(hv.x) && isfinite(hv.y);
-            const bool xo = h < a.nh && fin &&
-                            (hyp_exact_only(hv.x, hv.y) || !(fabsf(hv.x) < kMHypMax && fabsf(hv.y) < kMHypMax));
-            hxm |= xo ? 1u << j : 0u;
-            hfm |= (h < a.nh && fin && !xo) ? 1u << j : 0u;
-        }
+        // per set: fast / exact-only (bit j); half 0's word holds sets 0 and 2, half 1's sets 1 and 3
+        const auto cls = __builtin_amdgcn_permlane32_swap(own, own, false, false);
+        const uint32_t c02 = cls[0], c13 = cls[1];
+        const uint32_t hfm = (c02 & 1u) | ((c13 & 1u) << 1) | ((c02 & 2u) << 1) | ((c13 & 2u) << 2);
+        const uint32_t hxm = ((c02 >> 2) & 1u) | (((c13 >> 2) & 1u) << 1) | (((c02 >> 2) & 2u) << 1) | (((c13 >> 2) & 2u) << 2);
+        const bool any_xo = __builtin_amdgcn_ballot_w64(hxm != 0) != 0;   // wave-uniform
         int cnt[kMSet] = {0, 0, 0, 0};
         corr[lane] = 0;
         corr[64 + lane] = 0;
@@ -1016,8 +1024,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                 // |h'| + |c'| + 1 (the +1 covers the fp16 subnormal terms) for
                 // this origin; made again for the band pairs (not held across
                 // the hot loop)
-                auto hscale = [&](int j, float &hx, float &hy, float &s, float &Bv) {
-                    const bool fj = (hfm >> j) & 1u;
+                auto hscale = [&](int j, bool fj, float &hx, float &hy, float &s, float &Bv) {
                     const float2 hv = hlds[j * 32 + col];
                     hx = hv.x - ox;
                     hy = hv.y - oy;
@@ -1027,21 +1034,37 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                     s = __builtin_ldexpf(1.f, -k);
                     Bv = (__builtin_amdgcn_sqrtf(fmaf(hx, hx, hy * hy)) * 1.00001f + R) * 1.00001f + 1.f;
                 };
+                // The two lane halves hold the same columns: half 0 makes sets 0
+                // and 1, half 1 sets 2 and 3 (the same operations on the same
+                // values as one lane making all four), and v_permlane32_swap
+                // hands every lane its words of the other half's sets.  A set's
+                // fragment is {xh, xl | xh, yh} in half 0 and {yl, yh | s, s} in
+                // half 1: swap(a, b) returns (a's low half, b's low half) and
+                // (a's high half, b's high half), i.e. set i and set 2 + i with
+                // each consumer half's own word.
+                static_assert(kMSet == 4, "two sets per lane half");
                 h4f bf[kMSet];
                 float gb[kMSet];
 #pragma unroll
-                for (int j = 0; j < kMSet; ++j) {
+                for (int i = 0; i < 2; ++i) {
+                    const int j = 2 * half + i;                           // the set this lane makes
                     const bool fj = (hfm >> j) & 1u;
                     float hx, hy, s, Bv;
-                    hscale(j, hx, hy, s, Bv);
+                    hscale(j, fj, hx, hy, s, Bv);
                     const float hxs = hx * s, hys = hy * s;               // exact
                     const _Float16 xh_ = (_Float16)hxs, xl_ = (_Float16)(hxs - (float)xh_);
                     const _Float16 yh_ = (_Float16)hys, yl_ = (_Float16)(hys - (float)yh_);
                     const _Float16 sh = (_Float16)s;
-                    h4f f = half ? h4f{yl_, yh_, sh, sh} : h4f{xh_, xl_, xh_, yh_};
-                    if (!fj) f = h4f{(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
-                    bf[j] = f;
-                    gb[j] = fj ? (a.gzf + a.gzr) * Bv * s * 1.00001f : -1.f;
+                    const uint32_t w0 = fj ? pack_h2(xh_, xl_) : 0u, w1 = fj ? pack_h2(xh_, yh_) : 0u;
+                    const uint32_t w2 = fj ? pack_h2(yl_, yh_) : 0u, w3 = fj ? pack_h2(sh, sh) : 0u;
+                    const float g = fj ? (a.gzf + a.gzr) * Bv * s * 1.00001f : -1.f;
+                    const auto e0 = __builtin_amdgcn_permlane32_swap(w0, w2, false, false);
+                    const auto e1 = __builtin_amdgcn_permlane32_swap(w1, w3, false, false);
+                    const auto eg = __builtin_amdgcn_permlane32_swap(__float_as_uint(g), __float_as_uint(g), false, false);
+                    bf[i] = __builtin_bit_cast(h4f, make_uint2(e0[0], e1[0]));
+                    bf[i + 2] = __builtin_bit_cast(h4f, make_uint2(e0[1], e1[1]));
+                    gb[i] = __uint_as_float(eg[0]);
+                    gb[i + 2] = __uint_as_float(eg[1]);
                 }
                 uint32_t neg[kMSet] = {0u, 0u, 0u, 0u};
                 uint64_t hm0 = 0, hm1 = 0;              // band hits: bit 4 p + set, batches 0-15 / 16-31
@@ -1219,9 +1242,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                 flush();
                 __builtin_amdgcn_wave_barrier();
                 { const uint64_t t = cyc(); c_flush += t - c_mark; c_fix += t - c_mark; c_mark = t; }
-                // exact-only hypotheses (rare): lane = pixel, one hypothesis at a time
+                // exact-only hypotheses (rare: one wave-uniform test skips the
+                // sets' ballots): lane = pixel, one hypothesis at a time
 #pragma unroll
-                for (int j = 0; j < kMSet; ++j) {
+                for (int j = 0; any_xo && j < kMSet; ++j) {
                     uint64_t mm = __builtin_amdgcn_ballot_w64(((hxm >> j) & 1u) && half == 0);
                     nxo += __popcll(mm);
                     while (mm) {
