@@ -35,6 +35,7 @@
 // pv_common.h (constants, exact reference arithmetic, RNG, views, workspace,
 // reductions), pv_host.h (rc / last / cu_count).
 #include "pv_stages.h"
+#include "pv_band.h"
 
 #define PV_VERSION "pvvote 0.2 (gfx950)"
 
@@ -48,7 +49,12 @@
 
 #ifdef PVV_PROFILE
 namespace pvv __attribute__((visibility("hidden"))) {
-int g_abl = 0;   // pv_debug_set_ablation (pv_stages.h lists the bits)
+// pv_debug_set_ablation (pv_stages.h lists the bits); -DPVV_ABL_DEFAULT=M starts a
+// profiling build with mask M, for counter passes over a program that sets none
+#ifndef PVV_ABL_DEFAULT
+#define PVV_ABL_DEFAULT 0
+#endif
+int g_abl = PVV_ABL_DEFAULT;
 }
 #endif
 
@@ -108,6 +114,7 @@ struct VoteArgs {
     float thr, tau, gzf, gzr;
     uint64_t *trace;            // debug: per-wave (start, end) s_memrealtime stamps, or nullptr
     int32_t rw[4];              // SH, four resident rounds of blocks: work weights per round (0: even)
+    BandConsts bk;              // k_vote_mfma: the band re-check's constants (pv_band.h), made by launch_vote
 };
 
 // Share of unit w when the units come in four dispatch rounds of B = n / 4
@@ -1135,7 +1142,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
 #ifdef PVV_PROFILE   // ablation bit 64: band pairs keep the sign count's guess (counts wrong)
                 if (a.rw[3] == 7777) hm0 = hm1 = 0;
 #endif
-                const float kx = a.gzr / tau * 1.0001f, ky = a.gzr * 1.0001f;
                 // the queued pairs by the reference's sequence, one pair per lane;
                 // a decision the sign count got wrong corrects (set, column)
                 int nq = 0;
@@ -1170,15 +1176,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                 // tests/test_band_filter.py checks the inclusion in float32).  The pairs with t <= G' are queued for the
                 // reference's sequence: a superset of round 5's queue, so every
                 // decision still equals KU's.
-                // (1 / (1 - ky): ky reaches 8e-4 at thr 0.999999 -- gzr grows with 1/tau)
-                const float inv1k = 1.0002f / (1.f - ky * 1.0001f);
+                // K, and G' / gb, are functions of tau, gzf and gzr alone: made once on the
+                // host (a.bk, band_consts in pv_band.h: the same float32 expressions)
                 float Gs[kMSet];
-                const float gq = a.gzf / (a.gzf + a.gzr) * 1.0011f * inv1k;
 #pragma unroll
-                for (int j = 0; j < kMSet; ++j) Gs[j] = gb[j] * gq;
-                const float Kb = (kx + ky) * inv1k;
+                for (int j = 0; j < kMSet; ++j) Gs[j] = gb[j] * a.bk.gq;
+                const float Kb = a.bk.Kb;
+                // The candidates of flagged MFMA (batch p, set j) are the pairs with fj && pix < np
+                // && ts[q] <= G.  Only ts[q] <= G is a per-lane test; the other two are wave masks
+                // combined with its ballot in scalar registers:
+                // - fj, whether column col of set j is a fast hypothesis: one ballot per flagged MFMA;
+                // - pix < np, with pix = 16 p + off(q) + 2 half and off(q) = (q & 1) + 4 (q >> 1)
+                //   (the MFMA's row layout), fails only past the sub-chunk's last pixel, i.e. in
+                //   its last batch: with rem = np - 16 p pixels left from this batch on (>= 1, and
+                //   above 15 in every batch but the last, where both tests hold for every q),
+                //   slot q's pixel is inside for lane half 0 if off(q) < rem and for half 1 if
+                //   off(q) + 2 < rem.
+                // A queue entry is pix | j << 9 | col << 11 | the sign count's guess << 16: the
+                // lane's part (col, half) plus the wave-uniform part (p, j, the guess as 1) once per
+                // flagged MFMA, off(q) added per entry, and a negative z takes the guess back.
                 auto band_test = [&](const f32x16 &c, int p, int j) {
-                    const bool fj = (hfm >> j) & 1u;
+                    const uint64_t fmj = __builtin_amdgcn_ballot_w64((hfm >> j) & 1u);
                     // (selects on the wave-uniform j: a dynamic index would put Gs / bf in scratch)
                     const float G = j == 0 ? Gs[0] : j == 1 ? Gs[1] : j == 2 ? Gs[2] : Gs[3];
                     float zs[8], ts[8];
@@ -1195,16 +1213,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
 #ifdef PVV_PROFILE   // ablation bit 128: the candidates found but never queued (counts wrong)
                     if (a.rw[3] == 7778) mt = 3.0e38f;
 #endif
-                    if (__builtin_amdgcn_ballot_w64(fj && mt <= G)) {
+                    if ((__builtin_amdgcn_ballot_w64(mt <= G) & fmj) != 0) {
+                        const int rem = np - p * kMB;
+                        uint32_t eb = (((uint32_t)col << 11) | (2u * (uint32_t)half)) +
+                                      ((uint32_t)(p * kMB) | ((uint32_t)j << 9) | (1u << 16));
+                        // (opaque to the optimiser, which otherwise keeps the lane's part plus off(q)
+                        // in eight registers from the kernel's start)
+                        asm volatile("" : "+v"(eb));
 #pragma unroll
                         for (int q = 0; q < 8; ++q) {
-                            const int pix = p * kMB + (q & 1) + 4 * (q >> 1) + 2 * half;
-                            const bool u = fj && pix < np && ts[q] <= G;
-                            const uint64_t m = __builtin_amdgcn_ballot_w64(u);
+                            const int off = (q & 1) + 4 * (q >> 1);
+                            const uint64_t in = (off < rem ? 0x00000000ffffffffull : 0ull) |
+                                                (off + 2 < rem ? 0xffffffff00000000ull : 0ull);
+                            const uint64_t m = __builtin_amdgcn_ballot_w64(ts[q] <= G) & fmj & in;
                             if (m) {
                                 if (nq > kMQueue - kWave) flush();
-                                const int at = nq + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                                if (u) bq[at] = (uint32_t)pix | ((uint32_t)j << 9) | ((uint32_t)col << 11) | ((signbit(zs[q]) ? 0u : 1u) << 16);
+                                const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
+                                                                              __builtin_amdgcn_mbcnt_lo((uint32_t)m, (uint32_t)nq));
+                                const uint32_t neg = (uint32_t)((int32_t)__float_as_uint(zs[q]) >> 31);   // ~0: z's sign bit is set
+                                if (__builtin_amdgcn_inverse_ballot_w64(m)) bq[at] = eb + (uint32_t)off + (neg << 16);
                                 nq += __popcll(m);
                                 nqd += __popcll(m);
                             }
@@ -2149,6 +2176,8 @@ void launch_vote(const VoteArgs &va, int64_t pixel_steps, hipStream_t s) {
         const int grid = vote_grid_steps(pixel_steps, (const void *)k_vote_mfma<PREPPED>, PVV_VM_BPC);
         VoteArgs vr = va;
         vr.gzf = va.fast ? mfma_gz(va.tau) : 0.f;
+        // (!fast: tau = 0, every sub-chunk takes the slow path and reads none of them)
+        vr.bk = va.fast ? band_consts(vr.tau, vr.gzf, vr.gzr) : BandConsts{};
         for (int k = 0; k < 4; ++k) vr.rw[k] = 0;
         // (rw[3]: the sentinels of k_vote_mfma's two band ablations, profiling builds)
         if (g_abl & 128) vr.rw[3] = 7778;

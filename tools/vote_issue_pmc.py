@@ -3,8 +3,11 @@ issue-slot figures of DESIGN section 7b:
     vote_issue_pmc.py COUNTER_DIR OUT.json [CLOCK_GHZ (2.4)]
 Per launch: the counters' means, VALU instructions per wave, and the share of
 the SIMDs' cycles in which a VALU instruction (MFMA included) was issuing.
-SQ_ACTIVE_INST_VALU, SQ_BUSY_CYCLES, SQ_WAVE_CYCLES and
-SQ_VALU_MFMA_BUSY_CYCLES count quad-cycles (x 4 = shader cycles)."""
+SQ_ACTIVE_INST_VALU, SQ_BUSY_CYCLES and SQ_WAVE_CYCLES count quad-cycles (x 4 =
+shader cycles); SQ_VALU_MFMA_BUSY_CYCLES counts shader cycles (32 per 32x32 MFMA of
+8 passes), so it is not multiplied.  (profiles/vote_issue/pmc_*.json were written
+when this tool multiplied it too: their mfma_busy_share_of_simd_cycles is four
+times too high.)"""
 import collections
 import csv
 import glob
@@ -32,7 +35,8 @@ if durs:
     if "SQ_ACTIVE_INST_VALU" in m:
         d["valu_issue_share_of_simd_cycles"] = 4 * m["SQ_ACTIVE_INST_VALU"] / cyc
     if "SQ_VALU_MFMA_BUSY_CYCLES" in m:
-        d["mfma_busy_share_of_simd_cycles"] = 4 * m["SQ_VALU_MFMA_BUSY_CYCLES"] / cyc
+        d["mfma_busy_share_of_simd_cycles"] = m["SQ_VALU_MFMA_BUSY_CYCLES"] / cyc
+        d["mfma_busy_cycles_per_simd"] = m["SQ_VALU_MFMA_BUSY_CYCLES"] / SIMDS
 if m.get("SQ_WAVES"):
     d["valu_insts_per_wave"] = m.get("SQ_INSTS_VALU", 0.0) / m["SQ_WAVES"]
     if "SQ_ACTIVE_INST_VALU" in m and "SQ_WAVE_CYCLES" in m:
