@@ -1,13 +1,15 @@
 """PVNet's inference side on AMD Instinct: see README.md for the modules.
 
-The ground-truth side (pvnet_amd/render.py), model preparation (pvnet_amd/models.py) and the training
-loss (pvnet_amd/net_utils.py) are exported here, resolved on first use so that importing the package
-stays as cheap as it was."""
+The ground-truth side (pvnet_amd/render.py), model preparation (pvnet_amd/models.py), the training
+loss (pvnet_amd/net_utils.py) and the training augmentation (pvnet_amd/augment.py) are exported here, resolved on first use so that importing the package
+stays as cheap as it was.  The augmentation's hot-path entry point keeps its module's name in
+front of it, ``pvnet_amd.augment.apply``: a bare ``apply`` at package level would say nothing."""
 
 _RENDER = ("MeshTable", "render_labels", "vertex_field", "render_ground_truth", "mask_iou")
 _MODELS = ("extent", "farthest_points", "diameter", "corners_3d", "keypoints_3d")
 _LOSS = ("pvnet_loss",)
-__all__ = [*_RENDER, *_MODELS, *_LOSS]
+_AUGMENT = ("AugmentParams", "label_stats", "random_params", "transform_keypoints", "augment_ground_truth")
+__all__ = [*_RENDER, *_MODELS, *_LOSS, *_AUGMENT]
 
 
 def __getattr__(name):
@@ -20,4 +22,7 @@ def __getattr__(name):
     if name in _LOSS:
         from . import net_utils
         return getattr(net_utils, name)
+    if name in _AUGMENT:
+        from . import augment
+        return getattr(augment, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,5 +1,5 @@
-"""Build libpvvote.so, libpveval.so, libpvpose.so, libpvrender.so, libpvmodel.so and libpvloss.so (the HIP C-ABI
-libraries) in-tree for gfx950.
+"""Build libpvvote.so, libpveval.so, libpvpose.so, libpvrender.so, libpvmodel.so, libpvloss.so and
+libpvaugment.so (the HIP C-ABI libraries) in-tree for gfx950.
 
     python -m pvnet_amd.build            # or __graft_entry__.build()
 
@@ -50,6 +50,12 @@ LOSS_SRCS = [os.path.join(CSRC, "pvloss.hip")]
 LOSS_HDR = os.path.join(REPO, "include", "pvloss.h")
 LOSS_OUT = os.path.join(HERE, "libpvloss.so")
 LOSS_DEPS = (*LOSS_SRCS, LOSS_HDR)
+# the training-augmentation library (include/pvaugment.h), a seventh; one translation unit that
+# includes no other file of csrc/
+AUG_SRCS = [os.path.join(CSRC, "pvaugment.hip")]
+AUG_HDR = os.path.join(REPO, "include", "pvaugment.h")
+AUG_OUT = os.path.join(HERE, "libpvaugment.so")
+AUG_DEPS = (*AUG_SRCS, AUG_HDR)
 ARCH = os.environ.get("PVVOTE_ARCH", "gfx950")
 
 HIPCC_FLAGS = [
@@ -82,25 +88,25 @@ def hipcc() -> str:
 
 def stale(out: str) -> bool:
     """Is `out` missing, or older than any source under csrc/, a public header or this file?
-    For each library the other five's translation units and public headers do not count, and
-    libpvrender.so, libpvmodel.so and libpvloss.so, which include nothing else of csrc/, depend on
-    their own sources alone."""
+    For each library the other six's translation units and public headers do not count, and
+    libpvrender.so, libpvmodel.so, libpvloss.so and libpvaugment.so, which include nothing else of
+    csrc/, depend on their own sources alone."""
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    own = {RENDER_OUT: RENDER_DEPS, MODEL_OUT: MODEL_DEPS, LOSS_OUT: LOSS_DEPS}.get(out)
+    own = {RENDER_OUT: RENDER_DEPS, MODEL_OUT: MODEL_DEPS, LOSS_OUT: LOSS_DEPS, AUG_OUT: AUG_DEPS}.get(out)
     if own is not None:
         return any(os.path.getmtime(p) > t for p in (*own, __file__))
-    other = {OUT: (*EVAL_SRCS, EVAL_HDR, *POSE_DEPS, *RENDER_DEPS, *MODEL_DEPS, *LOSS_DEPS),
-             EVAL_OUT: (*SRCS, *POSE_DEPS, *RENDER_DEPS, *MODEL_DEPS, *LOSS_DEPS),
-             POSE_OUT: (*SRCS, *EVAL_SRCS, EVAL_HDR, *RENDER_DEPS, *MODEL_DEPS, *LOSS_DEPS)}.get(out, ())
+    other = {OUT: (*EVAL_SRCS, EVAL_HDR, *POSE_DEPS, *RENDER_DEPS, *MODEL_DEPS, *LOSS_DEPS, *AUG_DEPS),
+             EVAL_OUT: (*SRCS, *POSE_DEPS, *RENDER_DEPS, *MODEL_DEPS, *LOSS_DEPS, *AUG_DEPS),
+             POSE_OUT: (*SRCS, *EVAL_SRCS, EVAL_HDR, *RENDER_DEPS, *MODEL_DEPS, *LOSS_DEPS, *AUG_DEPS)}.get(out, ())
     deps = [os.path.join(CSRC, n) for n in os.listdir(CSRC) if n.endswith((".hip", ".h"))]
     return any(os.path.getmtime(p) > t for p in (*deps, HDR, EVAL_HDR, POSE_HDR, RENDER_HDR, __file__)
                if p not in other)
 
 
 def needs_build() -> bool:
-    return any(stale(o) for o in (OUT, EVAL_OUT, POSE_OUT, RENDER_OUT, MODEL_OUT, LOSS_OUT))
+    return any(stale(o) for o in (OUT, EVAL_OUT, POSE_OUT, RENDER_OUT, MODEL_OUT, LOSS_OUT, AUG_OUT))
 
 
 def _link(out: str, srcs, extra=()) -> None:
@@ -113,8 +119,8 @@ def _link(out: str, srcs, extra=()) -> None:
 
 
 def build(force: bool = False, extra=()) -> str:
-    """Build libpvvote.so, libpveval.so, libpvpose.so, libpvrender.so, libpvmodel.so and libpvloss.so
-    (each when stale); returns libpvvote.so's path."""
+    """Build libpvvote.so, libpveval.so, libpvpose.so, libpvrender.so, libpvmodel.so, libpvloss.so and
+    libpvaugment.so (each when stale); returns libpvvote.so's path."""
     if force or stale(OUT):
         _link(OUT, SRCS, extra)
     if force or stale(EVAL_OUT):
@@ -127,6 +133,8 @@ def build(force: bool = False, extra=()) -> str:
         _link(MODEL_OUT, MODEL_SRCS, extra)
     if force or stale(LOSS_OUT):
         _link(LOSS_OUT, LOSS_SRCS, extra)
+    if force or stale(AUG_OUT):
+        _link(AUG_OUT, AUG_SRCS, extra)
     return OUT
 
 
