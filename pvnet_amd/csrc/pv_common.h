@@ -24,6 +24,7 @@
 
 #include "../../include/pvvote.h"
 #include "pv_tunables.h"
+#include "pv_rng.h"
 
 namespace pvv __attribute__((visibility("hidden"))) {
 
@@ -130,33 +131,7 @@ __device__ __forceinline__ int lane_id() { return __lane_id(); }
 
 __device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
 
-// --------------------------------------------------------------------------
-// RNG (counter based; the reference uses torch's device RNG, which cannot be
-// reproduced -- parity tests inject idxs / keep-masks instead)
-// --------------------------------------------------------------------------
-__host__ __device__ inline uint64_t mix64(uint64_t z) {
-    z += 0x9e3779b97f4a7c15ull;
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-
-// 32-bit avalanche (lowbias32 constants); two rounds keyed by the seed
-__host__ __device__ inline uint32_t hash32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du;
-    x ^= x >> 15; x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-__device__ inline int32_t rand_index(uint64_t seed, uint64_t key, int32_t n) {
-    uint32_t r = hash32(hash32((uint32_t)key ^ (uint32_t)seed) + (uint32_t)(key >> 32) + (uint32_t)(seed >> 32));
-    return (int32_t)(((uint64_t)r * (uint32_t)n) >> 32);
-}
-
-__device__ inline float rand_unit(uint64_t seed, uint64_t key) {
-    return (float)(mix64(seed ^ mix64(key ^ 0x5bd1e995ull)) >> 40) * (1.0f / 16777216.0f);
-}
+// (the counter RNG -- mix64, hash32, rand_index, rand_unit -- is pv_rng.h, included above)
 
 // --------------------------------------------------------------------------
 // masks

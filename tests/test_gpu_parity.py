@@ -244,6 +244,51 @@ def test_vp_kernels(device, rv):
     np.testing.assert_array_equal(inl.cpu().numpy(), g["inliers"])
 
 
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_vp_kernels_random_match_oracle(seed, device, rv):
+    """k_generate_vp / k_vote_vp on random inputs in test_guard_band_stress's style (zero,
+    tiny and 2e19-scaled directions, so some hypotheses overflow to inf / NaN) against the
+    oracle's KU:170-310: hypotheses bit for bit (a NaN for a NaN: its sign and payload are
+    the hardware's), then the votes of those hypotheses with w = 0, zero and NaN ones put
+    in, over a pre-filled buffer -- bytes the vote does not set stay as they were."""
+    rng = np.random.default_rng(100 + seed)
+    tn, vn, hn = 1000, 3, 70
+    coords = np.stack([rng.integers(0, 640, tn), rng.integers(0, 480, tn)], 1).astype(np.float32)
+    ang = rng.uniform(-np.pi, np.pi, (tn, vn))
+    scale = rng.choice([1.0, 1e-7, 3e-7, 0.0, 1e5, 2e19], size=(tn, vn), p=[0.9, 0.02, 0.02, 0.02, 0.02, 0.02])
+    direct = np.stack([np.cos(ang) * scale, np.sin(ang) * scale], -1).astype(np.float32)
+    idxs = rng.integers(0, tn, (hn, vn, 2)).astype(np.int32)
+    idxs[0] = idxs[0, :, :1]                                # a pixel paired with itself
+    idxs[1, :, 0], idxs[1, :, 1] = 0, tn - 1
+    big = np.nonzero(scale[:, 0] == 2e19)[0]
+    zero = np.nonzero(scale[:, 0] == 0.0)[0]
+    assert len(big) >= 10 and len(zero) >= 1
+    idxs[2, 0] = (zero[0], 5)                               # a zero direction
+    idxs[3:8, 0] = big[:10].reshape(5, 2)                   # products that overflow
+    want = O.generate_hypothesis_vanishing_point(direct, coords, idxs)
+    got = rv.generate_hypothesis_vanishing_point(cu(direct, device), cu(coords, device), cu(idxs, device)).cpu().numpy()
+    assert (~np.isfinite(want)).any() and (want[..., 2] == 0).any() and np.isfinite(want).all(-1).sum() > hn * vn // 2
+
+    def canon(a):
+        return np.where(np.isnan(a), np.uint32(0x7fc00000), bits(a))
+    np.testing.assert_array_equal(canon(got), canon(want))
+    hyp = want.copy()
+    hyp[10, :, 2] = 0.0                                     # w = 0: a direction, not a point
+    hyp[11] = (1.0, -2.0, 0.0)
+    hyp[12] = 0.0
+    hyp[13] = np.nan
+    hyp[14, :, 2] = np.nan
+    hyp[15] = (320.0, 240.0, 1.0)                           # a finite point on a pixel centre
+    for thr in (0.99, 0.5):
+        init = (rng.random((hn, vn, tn)) < 0.3).astype(np.uint8) * 7
+        ref = init.copy()
+        O.voting_for_hypothesis_vanishing_point(direct, coords, hyp, ref, thr)
+        assert 0 < (ref == 1).sum() < ref.size // 2 and (ref[10] == 1).any() and (ref == 7).any()
+        out = cu(init, device)
+        rv.voting_for_hypothesis_vanishing_point(cu(direct, device), cu(coords, device), cu(hyp, device), out, thr)
+        np.testing.assert_array_equal(out.cpu().numpy(), ref, err_msg=f"thr={thr}")
+
+
 def test_input_checks(device, rv):
     d = torch.zeros(10, 3, 2, device=device)
     c = torch.zeros(10, 2, device=device)
