@@ -640,6 +640,11 @@ def _conv(x, c: nn.Conv2d):
     return F.conv2d(x, c.weight, None, c.stride, c.padding, c.dilation, c.groups)
 
 
+def _map2(fm: torch.Tensor) -> bool:
+    """At least 2 x 2: what pv_decoder_conv4s_f16 / _conv2s_f16 / _tail_f16 take (hin, win >= 2)."""
+    return fm.shape[2] >= 2 and fm.shape[3] >= 2
+
+
 class PVNetInference(nn.Module):
     """Channels-last inference form of a :class:`PVNet` (fp16: configs[2]'s
     backbone; f32: configs[1]'s): BatchNorm folded into the convolutions
@@ -795,7 +800,9 @@ class PVNetInference(nn.Module):
                 cat8 = conv_epilogue(_conv(y, r.fc[0]), r.fc[0].bias, "relu", skip=x8s)
             fm = self._conv_act(self.conv8s[0], cat8, "leaky")
         c4 = self.conv4s[0]
-        if (fm.dtype == torch.float16 and self.fused_conv and fm.shape[1] == 128 and x4s.shape[1] == 64
+        # the fused decoder kernels take maps of at least 2 x 2 (an 8 x W or H x 8 frame's stride-8
+        # map has one row or column: the upsample2x_cat + convolution form below takes it)
+        if (fm.dtype == torch.float16 and self.fused_conv and _map2(fm) and fm.shape[1] == 128 and x4s.shape[1] == 64
                 and c4.in_channels == 192 and c4.out_channels == 64 and c4.kernel_size == (3, 3)):
             key = (c4.weight.data_ptr(), c4.weight._version, c4.bias.data_ptr(), c4.bias._version)
             if getattr(self, "_c4s_key", None) != key:
@@ -806,7 +813,7 @@ class PVNetInference(nn.Module):
             fm = upsample2x_cat(fm, x4s, fm.shape[1] + x4s.shape[1])
             fm = conv_epilogue(_conv(fm, c4), c4.bias, "leaky")
         c2 = self.conv2s[0]
-        if (fm.dtype == torch.float16 and self.fused_conv and fm.shape[1] == 64 and x2s.shape[1] == 64
+        if (fm.dtype == torch.float16 and self.fused_conv and _map2(fm) and fm.shape[1] == 64 and x2s.shape[1] == 64
                 and c2.in_channels == 128 and c2.out_channels == 32 and c2.kernel_size == (3, 3)):
             key = (c2.weight.data_ptr(), c2.weight._version, c2.bias.data_ptr(), c2.bias._version)
             if getattr(self, "_c2s_key", None) != key:     # the kernel's weight layout, made once
@@ -818,7 +825,7 @@ class PVNetInference(nn.Module):
             fm = conv_epilogue(_conv(fm, c2), c2.bias, "leaky")
         c0, c1 = self.convraw[0], self.convraw[3]
         slope = self.convraw[2].negative_slope
-        if x.dtype == torch.float16 and self.fused_tail:
+        if x.dtype == torch.float16 and self.fused_tail and _map2(fm):
             key = (c0.weight.data_ptr(), c0.weight._version, c0.bias.data_ptr(), c0.bias._version,
                    c1.weight.data_ptr(), c1.weight._version, c1.bias.data_ptr(), c1.bias._version)
             if getattr(self, "_tail_key", None) != key:     # matrix-core layouts of convraw's weights, made once

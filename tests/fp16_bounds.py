@@ -1,5 +1,6 @@
 """Elementwise error bounds for the fp16 convolution kernels against an fp32
-convolution of the same fp16 inputs (tests/test_backbone.py).
+convolution of the same fp16 inputs (tests/test_backbone.py,
+tests/test_gpu_backbone_edges.py).
 
 A kernel's output differs from the fp32 reference only by
   * the f32 accumulation order: the products of fp16 operands are exact in
@@ -70,3 +71,32 @@ def check(got: torch.Tensor, ref: torch.Tensor, bound: torch.Tensor, name: str) 
           f"largest dev / bound {r:.3f} (bound median {float(bound.median()):.2e})")
     assert bool((d <= bound).all()), f"{name}: {int((d > bound).sum())} elements outside the fp32 bound"
     return r
+
+
+def check_decoder_fp64(got, fm, skip, c, slope, name, head=None):
+    """A decoder kernel against the f64 reference of the same fp16 inputs:
+    upsample x2 (align_corners) + cat + 3x3 conv + bias + LeakyReLU (+ the 1x1
+    head conv + bias), bounded by the fp16 blend (BLEND x the blended sources'
+    largest |fm|, through sum |w|), the f32 accumulation and each fp16
+    rounding of the epilogue (this module)."""
+    with torch.no_grad():
+        up = F.interpolate(fm.double(), scale_factor=2, mode="bilinear", align_corners=True)
+        xin = torch.cat([up, skip.double()], 1)
+        cin = xin.shape[1]
+        c64 = conv64(xin, c.weight, padding=1)
+        eb = torch.cat([BLEND * blend_source_max(fm), torch.zeros_like(skip, dtype=torch.float64)], 1)
+        e = conv64(eb, c.weight.abs(), padding=1) + acc_bound(xin, c.weight, 9 * cin, padding=1)
+        e = round_step(c64, e)                                      # the conv's fp16 output
+        y64 = c64 + c.bias.double().view(1, -1, 1, 1)
+        e = round_step(y64, e)                                      # + bias (fp16 add)
+        e = leaky_step(y64, e, slope)
+        y64 = F.leaky_relu(y64, slope)
+        if head is not None:                                        # the tail's 1x1 conv + bias
+            w2, b2 = head
+            k = w2.shape[1]
+            e = conv64(e, w2.abs()) + acc_bound(y64, w2, k)
+            y64 = conv64(y64, w2)
+            e = round_step(y64, e)
+            y64 = y64 + b2.double().view(1, -1, 1, 1)
+            e = round_step(y64, e)
+    check(got, y64, e, name)

@@ -27,6 +27,7 @@ import torch
 from pvnet_amd.network import PVNet, PVNetInference, fold_batchnorm, upsample2x_cat
 from tests import backbone_init as BI
 from tests import fp16_bounds as B
+from tests.fp16_bounds import check_decoder_fp64 as _check_decoder_fp64
 from tests.golden_io import load
 
 G = load("backbone_g4")
@@ -785,36 +786,6 @@ def test_decoder_conv4s_matches_torch(hw, device):
     assert float(d.max()) <= 2 ** -7 * sc
     assert float(d.mean()) <= 2 ** -12 * sc
     _check_decoder_fp64(got, fm, skip, c, 0.1, "decoder conv4s")
-
-
-def _check_decoder_fp64(got, fm, skip, c, slope, name, head=None):
-    """A decoder kernel against the f64 reference of the same fp16 inputs:
-    upsample x2 (align_corners) + cat + 3x3 conv + bias + LeakyReLU (+ the 1x1
-    head conv + bias), bounded by the fp16 blend (BLEND x the blended sources'
-    largest |fm|, through sum |w|), the f32 accumulation and each fp16
-    rounding of the epilogue (tests/fp16_bounds.py)."""
-    F = torch.nn.functional
-    with torch.no_grad():
-        up = F.interpolate(fm.double(), scale_factor=2, mode="bilinear", align_corners=True)
-        xin = torch.cat([up, skip.double()], 1)
-        cin = xin.shape[1]
-        c64 = B.conv64(xin, c.weight, padding=1)
-        eb = torch.cat([B.BLEND * B.blend_source_max(fm), torch.zeros_like(skip, dtype=torch.float64)], 1)
-        e = B.conv64(eb, c.weight.abs(), padding=1) + B.acc_bound(xin, c.weight, 9 * cin, padding=1)
-        e = B.round_step(c64, e)                                    # the conv's fp16 output
-        y64 = c64 + c.bias.double().view(1, -1, 1, 1)
-        e = B.round_step(y64, e)                                    # + bias (fp16 add)
-        e = B.leaky_step(y64, e, slope)
-        y64 = F.leaky_relu(y64, slope)
-        if head is not None:                                        # the tail's 1x1 conv + bias
-            w2, b2 = head
-            k = w2.shape[1]
-            e = B.conv64(e, w2.abs()) + B.acc_bound(y64, w2, k)
-            y64 = B.conv64(y64, w2)
-            e = B.round_step(y64, e)
-            y64 = y64 + b2.double().view(1, -1, 1, 1)
-            e = B.round_step(y64, e)
-    B.check(got, y64, e, name)
 
 
 def test_stem_weight_layout():
