@@ -18,7 +18,8 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 # the translation units (csrc/pvvote.hip's head comment maps the vote library's)
 SRCS = [os.path.join(CSRC, n) for n in (
-    "pvvote.hip", "pvcompact.hip", "pvrefine.hip", "pvevd.hip", "pvpnp.hip", "pvdecoder.hip", "pvconv.hip")]
+    "pvvote.hip", "pvapi.hip", "pvpipeline.hip", "pvcompact.hip", "pvrefine.hip", "pvevd.hip", "pvpnp.hip",
+    "pvdecoder.hip", "pvconv.hip")]
 HDR = os.path.join(REPO, "include", "pvvote.h")
 OUT = os.path.join(HERE, "libpvvote.so")
 # the pose-evaluation library (include/pveval.h): a library of its own, so libpvvote.so's

@@ -131,6 +131,17 @@ __device__ __forceinline__ int lane_id() { return __lane_id(); }
 
 __device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
 
+__device__ __forceinline__ float bcast(float x, int lane) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), lane));
+}
+
+// plain POD read through the constant address space -> s_load (scalar) loads
+struct alignas(16) F4 { float x, y, z, w; };
+
+// operands and result of v_mfma_f32_32x32x8_f16 (k_vote_mfma, k_debug_mfma_sums)
+typedef _Float16 h4f __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
 // (the counter RNG -- mix64, hash32, rand_index, rand_unit -- is pv_rng.h, included above)
 
 // --------------------------------------------------------------------------

@@ -1,9 +1,10 @@
-// pv_stages.h -- what the stages that have their own translation unit expose
-// to the pipeline (pvvote.hip): each stage's host launcher and its argument
+// pv_stages.h -- what the stages, each in its own translation unit, expose to
+// the pipeline (pvpipeline.hip): each stage's host launcher and its argument
 // struct.  Internal to libpvvote.so (namespace pvv, hidden visibility); the
 // exported C ABI is include/pvvote.h.
 #pragma once
 
+#include "pv_band.h"
 #include "pv_common.h"
 #include "pv_host.h"
 
@@ -51,6 +52,41 @@ struct CompactArgs {
 
 // k_fg_count + k_compact (+ the fused hypotheses) of one call
 int compact(const CompactArgs &a);
+
+// ---- hypotheses and the fused vote/count (pvvote.hip) ---------------------
+constexpr int kHypLane = 2;                 // hypotheses per lane of a vote wave
+constexpr int kGroup = kWave * kHypLane;    // hypotheses per wave: a hypothesis group, the unit of the vote's work index
+
+struct VoteArgs {
+    const float4 *pex;          // PREPPED: exact data (cx, cy, nx, ny), same layout
+    const float2 *coords;       // !PREPPED: coords[b*P + t]
+    const float2 *raw;          // !PREPPED: raw[b*vn*P + v*raw_v + t*raw_t]
+    const float2 *hyp;          // !GEN: hyp[b*hyp_sb + v*hyp_sv + h*hyp_sh]
+    float2 *hyp_out;            // GEN: generated hypotheses [b][nh][vn]
+    float2 *hypv_out;           // k_hyp_gen: keypoint-major copy [b][vn][nh]
+    int64_t hyp_sb, hyp_sv, hyp_sh;
+    float *diag_hyp;            // GEN: optional copy [b][nh][vn][2]
+    const int32_t *idxs;        // GEN: pixel pairs [b][nh][vn][2], or nullptr (counter RNG)
+    int32_t *counts;            // counts[b*cnt_bs + v*cnt_v + h*cnt_h]
+    const int32_t *tn_dev;      // [b] pixels per image, or nullptr (tn_host)
+    uint64_t seed;
+    int32_t P, raw_v, raw_t, cnt_v, cnt_h, cnt_bs;
+    int32_t tn_host, b, vn, nh, hgn, fast;
+    int32_t b0;                 // GEN: batch index of image 0 of this launch (RNG key: the same pairs in any chunking)
+    float thr, tau, gzf, gzr;
+    uint64_t *trace;            // debug: per-wave (start, end) s_memrealtime stamps, or nullptr
+    int32_t rw[4];              // SH, four resident rounds of blocks: work weights per round (0: even)
+    BandConsts bk;              // k_vote_mfma: the band re-check's constants (pv_band.h), made by launch_vote
+};
+
+// thr, tau, gzf, gzr and fast of `va` from the inlier threshold (the byte kernel takes its own from a scratch VoteArgs)
+void fast_constants(float thr, VoteArgs *va);
+// does the pipeline pre-generate the hypotheses (keypoint-major in w.hypv: k_hyp_gen or k_compact's first blocks)?
+bool hyp_pregen_used(int nh);
+// k_hyp_gen over va's b images: hyp_out and hypv_out
+void launch_hyp_gen(const VoteArgs &va, hipStream_t s);
+// the fused vote/count of one launch chunk on compacted pixels (va.pex): k_vote_mfma, or k_vote_count
+void launch_pipeline_vote(const VoteArgs &va, int64_t pixel_steps, hipStream_t s);
 
 // ---- refine and v5 confidence (pvrefine.hip) ------------------------------
 // k_refine_solve over the workspace's counts; hypv: the hypotheses keypoint-major (w.hypv)

@@ -1,7 +1,7 @@
 // pv_tunables.h -- every numeric default of the voting library that a build
 // may override (tools/build_variant.py NAME -DMACRO=V passes its defines to
 // every translation unit), each with the measurement behind it.  One place,
-// so that the kernels and pv_build_config() (pvvote.hip) cannot disagree.
+// so that the kernels and pv_build_config() (pvpipeline.hip) cannot disagree.
 // DESIGN.md section 7 has the A/B records; the variants measured and removed
 // are in DESIGN.md's appendix "Removed variants".
 #pragma once

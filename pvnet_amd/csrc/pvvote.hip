@@ -25,19 +25,21 @@
 //     by the API entry point voting_for_hypothesis, as coalesced 8-byte
 //     stores (lane = 8 pixels, hypotheses broadcast from LDS).
 //
-// Files: this one holds the fused vote/count kernels, the stand-alone API
-// kernels, the pipeline and the C ABI.  The stages before and after the vote
-// have their own translation units, reached through pv_stages.h:
+// Files: this one holds the fused vote/count -- k_vote_mfma, k_vote_count,
+// k_hyp_gen, their host side (fast_constants, launch_vote) and the entries
+// that are the vote's own (pv_vote_counts, two debug hooks).  Every stage has
+// its own translation unit, reached by the pipeline through pv_stages.h:
+//   pvpipeline.hip the pipeline (front_half, v3 / v5 / motion / EVD) and the
+//                  general C ABI (version, build config, errors, streams)
 //   pvcompact.hip  k_fg_count, k_compact (+ the fused hypotheses)
 //   pvrefine.hip   k_refine_solve, k_point_conf (v5 confidence)
 //   pvevd.hip      k_evd_with_mean, k_evd_topk, k_motion_vote
+//   pvapi.hip      the stand-alone API kernels the pipeline never launches:
+//                  k_generate_api, k_vote_bytes (byte masks), VP, debug kernels
 // Shared headers: pv_tunables.h (every -D default with its measurement),
 // pv_common.h (constants, exact reference arithmetic, RNG, views, workspace,
 // reductions), pv_host.h (rc / last / cu_count).
 #include "pv_stages.h"
-#include "pv_band.h"
-
-#define PV_VERSION "pvvote 0.2 (gfx950)"
 
 // Per-wave timestamp traces (tools/vote_trace.py, tools/compact_trace.py)
 // exist only in trace builds (-DPVV_TRACE); the product kernels carry none.
@@ -45,17 +47,6 @@
 #define PVV_TRACE_ON(a) ((a).trace != nullptr)
 #else
 #define PVV_TRACE_ON(a) false
-#endif
-
-#ifdef PVV_PROFILE
-namespace pvv __attribute__((visibility("hidden"))) {
-// pv_debug_set_ablation (pv_stages.h lists the bits); -DPVV_ABL_DEFAULT=M starts a
-// profiling build with mask M, for counter passes over a program that sets none
-#ifndef PVV_ABL_DEFAULT
-#define PVV_ABL_DEFAULT 0
-#endif
-int g_abl = PVV_ABL_DEFAULT;
-}
 #endif
 
 namespace {
@@ -91,32 +82,6 @@ using namespace pvv;
 // bound's domain) are re-decided with the reference's exact sequence.  See
 // DESIGN.md "Exactness of the fast vote test" for the derivation.
 // ==========================================================================
-// plain PODs read through the constant address space -> s_load (scalar) loads
-struct alignas(16) F4 { float x, y, z, w; };
-struct alignas(8) F2 { float x, y; };
-
-struct VoteArgs {
-    const float4 *pex;          // PREPPED: exact data (cx, cy, nx, ny), same layout
-    const float2 *coords;       // !PREPPED: coords[b*P + t]
-    const float2 *raw;          // !PREPPED: raw[b*vn*P + v*raw_v + t*raw_t]
-    const float2 *hyp;          // !GEN: hyp[b*hyp_sb + v*hyp_sv + h*hyp_sh]
-    float2 *hyp_out;            // GEN: generated hypotheses [b][nh][vn]
-    float2 *hypv_out;           // k_hyp_gen: keypoint-major copy [b][vn][nh]
-    int64_t hyp_sb, hyp_sv, hyp_sh;
-    float *diag_hyp;            // GEN: optional copy [b][nh][vn][2]
-    const int32_t *idxs;        // GEN: pixel pairs [b][nh][vn][2], or nullptr (counter RNG)
-    int32_t *counts;            // counts[b*cnt_bs + v*cnt_v + h*cnt_h]
-    const int32_t *tn_dev;      // [b] pixels per image, or nullptr (tn_host)
-    uint64_t seed;
-    int32_t P, raw_v, raw_t, cnt_v, cnt_h, cnt_bs;
-    int32_t tn_host, b, vn, nh, hgn, fast;
-    int32_t b0;                 // GEN: batch index of image 0 of this launch (RNG key: the same pairs in any chunking)
-    float thr, tau, gzf, gzr;
-    uint64_t *trace;            // debug: per-wave (start, end) s_memrealtime stamps, or nullptr
-    int32_t rw[4];              // SH, four resident rounds of blocks: work weights per round (0: even)
-    BandConsts bk;              // k_vote_mfma: the band re-check's constants (pv_band.h), made by launch_vote
-};
-
 // Share of unit w when the units come in four dispatch rounds of B = n / 4
 // blocks each weighted rw[r]: a SIMD issues age-first, so a CU's first-
 // dispatched block runs ahead of its later ones; weighting the earlier
@@ -197,11 +162,6 @@ __device__ __forceinline__ void even_share(uint32_t total, uint32_t nwaves, uint
     *hi = *lo + q + (w < rem ? 1u : 0u);
 }
 
-__device__ __forceinline__ float bcast(float x, int lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), lane));
-}
-
-
 // fast data of one pixel from its raw direction (API path without a prepped array)
 __device__ __forceinline__ float4 prep_pixel(float cx, float cy, float nx, float ny) {
     float n1 = sqrtf(nx * nx + ny * ny);                 // exactly the reference's norm1
@@ -230,7 +190,7 @@ __device__ __forceinline__ bool pixel_exotic(float nx, float ny) {
 }
 
 // One segment = pixels [ts, te) of one (image b, keypoint v, hypothesis group
-// hg) against the group's kGroup hypotheses (kHypLane per lane).
+// hg) against the group's kGroup hypotheses (kHypLane per lane; pv_stages.h).
 //
 // Pixels are staged per sub-chunk of 256 in two LDS slabs of the wave: the
 // fast operands (ux, uy, -k1, -k2) with k1 = u.c', k2 = u x c' and c' = c - o
@@ -242,8 +202,6 @@ __device__ __forceinline__ bool pixel_exotic(float nx, float ny) {
 // The band is gzf * B + gzr * D: B >= |h'| + |c'| bounds the fast path's own
 // rounding (per sub-chunk), D >= |h - c| the reference's (per 64-pixel
 // quarter, from the quarter's bounding box).
-constexpr int kHypLane = 2;
-constexpr int kGroup = kWave * kHypLane;
 
 // The wave's slab of exact operands.  Pipeline pixels are integer centres
 // below 65536 (check_desc), packed as cx | cy << 16: 12 B per pixel keeps a
@@ -797,9 +755,6 @@ __global__ __launch_bounds__(256) void k_hyp_gen(VoteArgs a) {
 // pair's own distance D, and decided by the reference's sequence when
 // inside it -- every decision equals KU:116-125's.
 // ==========================================================================
-typedef _Float16 h4f __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kMB = 16;                        // pixels per MFMA batch (32 rows: 16 pixels x (X, Y))
 // pixels per sub-chunk and band pairs queued per wave: pv_tunables.h
 constexpr int kMChunk = PVM_CHUNK;
@@ -1348,777 +1303,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
     }
 }
 
-// ==========================================================================
-// drop-in kernels on the reference layouts
-// ==========================================================================
-
-// KU:11-86
-__global__ __launch_bounds__(256) void k_generate_api(const float *direct, const float *coords, const int32_t *idxs,
-                                                      float *hypo, int tn, int vn, int hn) {
-    int hv = blockIdx.x * 256 + threadIdx.x;
-    if (hv >= hn * vn) return;
-    int hi = hv / vn, vi = hv - hi * vn;
-    int t0 = idxs[hi * vn * 2 + vi * 2], t1 = idxs[hi * vn * 2 + vi * 2 + 1];
-    float x = 0.f, y = 0.f, ox, oy;
-    if (t0 >= 0 && t0 < tn && t1 >= 0 && t1 < tn &&
-        exact_intersect(direct[t0 * vn * 2 + vi * 2], direct[t0 * vn * 2 + vi * 2 + 1], coords[t0 * 2],
-                        coords[t0 * 2 + 1], direct[t1 * vn * 2 + vi * 2], direct[t1 * vn * 2 + vi * 2 + 1],
-                        coords[t1 * 2], coords[t1 * 2 + 1], &ox, &oy)) {
-        x = ox; y = oy;
-    }
-    hypo[hi * vn * 2 + vi * 2] = x;
-    hypo[hi * vn * 2 + vi * 2 + 1] = y;
-}
-
-// KU:88-167 with byte outputs: inliers[h][v][t] (U1, store-bound: hn*vn*tn
-// bytes).  Mode OR writes only the inlier bytes (reference semantics: the
-// caller's buffer keeps its other bytes), DENSE writes every byte.
-//
-// A wave takes one item: keypoint v, a window of 512 pixels w and 64
-// consecutive hypotheses; lane l owns pixels t = 512w + 8l + j, j < 8, and
-// writes their 8 bytes of each row (h, v) at R = (h*vn + v)*tn + t with one
-// 8-byte store, unaligned as the rows are (measured as fast as aligned
-// stores on gfx950).  One item per wave, every item's operand loads at the
-// start of the launch, before the store stream fills the memory system.
-// There is no prepass: with hn a multiple of 256 a block's four waves take
-// four hypothesis groups of one window and stage the window once (raw
-// operands, fast operands and the window's frame, in LDS); the grid is
-// CU-balanced (full blocks a multiple of the CU count, the rest as quarter
-// blocks).  The vote test is vote_segment's rotated-frame test (5 FMAs per
-// pair); the inlier bytes are the signs of -z gathered with v_perm.  Pairs
-// inside the guard band go to a per-wave LDS queue decided by the
-// reference's sequence at the wave's end; hypotheses / pixels outside the
-// fast domain take it for their whole row.
-constexpr int kBytePix = 8;
-constexpr int kByteWin = kWave * kBytePix;      // bytes of a row per segment
-constexpr int kByteHB = PVV_BYTE_HB;             // hypothesis records per batch (rows per wave, <= 64)
-static_assert(kByteHB <= 64 && kByteHB % 16 == 0, "row masks are 64-bit; quarter blocks take 16 rows");
-constexpr uint32_t kQueuePerWave = 128;          // band pairs a wave queues for its end (LDS)
-
-#ifdef PVVOTE_TRACE_U1
-__device__ uint64_t *g_btrace;      // debug build only: per-wave phase stamps of k_vote_bytes
-#endif
-
-struct ByteArgs {
-    const float *direct;   // [tn][vn][2]
-    const float *coords;   // [tn][2]
-    const float *hypo;     // [hn][vn][2]
-    uint8_t *out;          // [hn][vn][tn]
-    int tn, vn, hn, nwin, nhg, fast;
-    float thr, tau, gzf, gzr;
-    int dbg;               // test hook (pv_debug_set_bytes_mode): 4 = one-entry band queue
-    int xcd;               // XCD-contiguous item ranges (grid a multiple of 8)
-    // CU-balanced grid (bal_nt > 0): bal_t full blocks, then bal_nt quarter
-    // blocks; per XCD bal_tnx / bal_ttx of each (see k_vote_bytes)
-    int bal_t, bal_nt, bal_tnx, bal_ttx;
-};
-
-// Operands of pixel (t, v) in the byte-output kernel, made where they are
-// staged (no prepass): (ux, uy, cx, cy) with u the direction rounded per
-// component; (0, 0) for a pixel that never votes (norm1 < 1e-6 or NaN,
-// KU:119-121, or non-finite coordinates) and ux = NaN for one outside the
-// fast domain.
-__device__ __forceinline__ float4 api_pixel(const float2 c, const float2 d) {
-    const float n1 = sqrtf(d.x * d.x + d.y * d.y);
-    const bool ok = !below_1e6(n1) && n1 == n1 && isfinite(c.x) && isfinite(c.y);
-    const float rs = __builtin_amdgcn_rsqf(fmaf(d.x, d.x, d.y * d.y));
-    float4 q = make_float4(0.f, 0.f, c.x, c.y);
-    if (ok)
-        q = (n1 <= kN1Max) ? make_float4(d.x * rs, d.y * rs, c.x, c.y)
-                           : make_float4(__builtin_nanf(""), 0.f, c.x, c.y);
-    return q;
-}
-__device__ __forceinline__ float2 api_coords(const ByteArgs &a, int t) {
-    return *(const float2 *)(a.coords + (int64_t)t * 2);
-}
-__device__ __forceinline__ float2 api_direct(const ByteArgs &a, int t, int v) {
-    return *(const float2 *)(a.direct + ((int64_t)t * a.vn + v) * 2);
-}
-
-// Issue priority from the rows a wave still has (0..3), as in vote_segment:
-// otherwise the SIMD favours its oldest wave, equal shares finish staggered
-// and the last waves of each SIMD run alone at a fraction of the issue rate.
-// (levels 0..2: 3 is the setup's, above every hot loop)
-__device__ __forceinline__ void prio_by_remaining(uint32_t remaining, uint32_t total) {
-    const uint64_t r3 = (uint64_t)remaining * 3, w1 = (uint64_t)total + 1;
-    if (r3 >= 2 * w1) __builtin_amdgcn_s_setprio(2);
-    else if (r3 >= w1) __builtin_amdgcn_s_setprio(1);
-    else __builtin_amdgcn_s_setprio(0);
-}
-
-// A window's fast-test frame, shared by the waves that vote it: origin o
-// (an integer point), the voting pixels' bounding box relative to o and its
-// radius R >= |c - o|; slow = some pixel is outside the fast domain.
-struct WinInfo {
-    float ox, oy, bxl, bxh, byl, byh, Rw;
-    int slow;
-};
-
-// rows h0 + i, i < nh (<= kByteHB), of keypoint v, pixels of window w
-template <int MODE>
-__device__ __forceinline__ void vote_bytes_seg(const ByteArgs &a, F4 *recs, uint8_t *band8, int v, int w, int h0,
-                                               int nh, uint32_t rem_after, uint32_t wave_total, uint16_t *wq,
-                                               uint32_t &qn, uint64_t *tsetup, const float4 *stage, float2 hq,
-                                               const float4 *raw, const float2 *hraw, const WinInfo *win) {
-    const uint32_t qcap = a.dbg == 4 ? 1u : kQueuePerWave;   // (dbg 4: test hook, a full queue)
-    const int lane = lane_id();
-    const float ntau = -a.tau;
-    const int tb = kByteWin * w + kBytePix * lane;              // lane's first pixel
-    const int64_t rstep = (int64_t)a.vn * a.tn;                 // R(h + 1) - R(h)
-    // row i's bytes of this lane: wave-uniform offset (SGPRs) + 32-bit lane offset
-    int64_t obase = ((int64_t)h0 * a.vn + v) * a.tn + (int64_t)kByteWin * w;
-    obase = (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(obase >> 32)) << 32 |
-                      (uint32_t)__builtin_amdgcn_readfirstlane((int)obase));   // (SGPRs for the asm below)
-    const uint32_t loff = kBytePix * lane;
-
-    // ---- operands ----
-    // hq: lane's hypothesis (row h0 + lane), loaded by the caller with the pixels
-    uint32_t vmask = 0;
-    float fu[kBytePix], fv[kBytePix], fk1[kBytePix], fk2[kBytePix];
-    float ox = 0.f, oy = 0.f, Rw = 0.f, bxl = 0.f, bxh = 0.f, byl = 0.f, byh = 0.f;
-    bool slow;
-    if (stage) {
-        // block-staged window: the fast operands and the window's bounds are
-        // made once per block (stage_window); pixels past tn never vote
-#pragma unroll
-        for (int j = 0; j < kBytePix; ++j) {
-            fu[j] = fv[j] = fk2[j] = 0.f;
-            fk1[j] = -1.0e30f;
-            if (tb + j < a.tn) {
-                const float4 q = stage[j * kWave + lane];
-                fu[j] = q.x; fv[j] = q.y; fk1[j] = q.z; fk2[j] = q.w;
-                vmask |= 1u << j;
-            }
-        }
-        slow = __builtin_amdgcn_readfirstlane(!a.fast || win->slow);
-        ox = win->ox; oy = win->oy; Rw = win->Rw;
-        bxl = win->bxl; bxh = win->bxh; byl = win->byl; byh = win->byh;
-        __syncthreads();   // the staging area is the block's band masks from here on
-    } else {
-        // from the caller's arrays: all 16 loads in flight, then the operands
-        uint32_t okmask = 0;
-        bool exo = false;
-        float2 c[kBytePix], d[kBytePix];
-#pragma unroll
-        for (int j = 0; j < kBytePix; ++j) {
-            const int t = tb + j;
-            c[j] = d[j] = make_float2(0.f, 0.f);
-            if (t < a.tn) {
-                c[j] = api_coords(a, t);
-                d[j] = api_direct(a, t, v);
-                vmask |= 1u << j;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < kBytePix; ++j) {
-            const float4 q = api_pixel(c[j], d[j]);
-            const bool in = vmask >> j & 1;
-            fu[j] = in ? q.x : 0.f; fv[j] = in ? q.y : 0.f; fk1[j] = in ? q.z : 0.f; fk2[j] = in ? q.w : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < kBytePix; ++j) {
-            exo |= fu[j] != fu[j];                                  // outside the fast domain
-            if (fu[j] != 0.f || fv[j] != 0.f) okmask |= 1u << j;    // votes at all
-        }
-        slow = __builtin_amdgcn_readfirstlane(!a.fast || __builtin_amdgcn_ballot_w64(exo) != 0);
-        // origin: an integer point at the first voting pixel; the voting pixels'
-        // bounding box relative to it (R >= |c - o|, and D >= |h - c| per row)
-        const uint64_t anyok = __builtin_amdgcn_ballot_w64(okmask != 0);
-        if (anyok) {
-            const int l0 = __builtin_ctzll(anyok);
-            const int j0 = __builtin_ctz(__builtin_amdgcn_readlane(okmask, l0));
-            float fx = fk1[0], fy = fk2[0];
-#pragma unroll
-            for (int j = 1; j < kBytePix; ++j)
-                if (j == j0) { fx = fk1[j]; fy = fk2[j]; }
-            ox = floorf(bcast(fx, l0));
-            oy = floorf(bcast(fy, l0));
-            float xl = 3.0e38f, xh = -3.0e38f, yl = 3.0e38f, yh = -3.0e38f;
-#pragma unroll
-            for (int j = 0; j < kBytePix; ++j)
-                if (okmask >> j & 1) {
-                    xl = fminf(xl, fk1[j] - ox); xh = fmaxf(xh, fk1[j] - ox);
-                    yl = fminf(yl, fk2[j] - oy); yh = fmaxf(yh, fk2[j] - oy);
-                }
-            bxl = wave_min(xl); bxh = wave_max(xh);
-            byl = wave_min(yl); byh = wave_max(yh);
-            const float ax = fmaxf(-bxl, bxh), ay = fmaxf(-byl, byh);
-            Rw = __builtin_amdgcn_sqrtf(fmaf(ax, ax, ay * ay)) * 1.00001f;
-        }
-        // fast operands (ux, uy, -k1, -k2) relative to the origin, in place;
-        // pixels that never vote get u = 0, -k1 = -1e30: -z = 1e30 tau, far
-        // above the band, for every finite h'
-#pragma unroll
-        for (int j = 0; j < kBytePix; ++j) {
-            const bool ok = okmask >> j & 1;
-            const float ux = fu[j], uy = fv[j];
-            const float cx = fk1[j] - ox, cy = fk2[j] - oy;
-            fu[j] = ok ? ux : 0.f;
-            fv[j] = ok ? uy : 0.f;
-            fk1[j] = ok ? -fmaf(ux, cx, uy * cy) : -1.0e30f;
-            fk2[j] = ok ? -fmaf(ux, cy, -(uy * cx)) : 0.f;
-        }
-    }
-    // hypothesis records (lane i -> row h0 + 8i): h - o, band, exact flag
-    uint64_t flagged;                                   // rows the exact pass decides whole
-    {
-        // (flagged rows carry an infinite band, so the hot loop defers them
-        // without testing the flag)
-        F4 rec{0.f, 0.f, __builtin_inff(), 1.f};
-        if (lane < nh) {
-            // non-finite or outside the fast domain: the exact sequence decides
-            const bool xo = !(isfinite(hq.x) && isfinite(hq.y)) || hyp_exact_only(hq.x, hq.y);
-            if (!xo && !slow) {
-                const float hx = hq.x - ox, hy = hq.y - oy;
-                const float B = (__builtin_amdgcn_sqrtf(fmaf(hx, hx, hy * hy)) + Rw) * 1.00001f + 1e-30f;
-                const float dx = fmaxf(fabsf(hx - bxl), fabsf(hx - bxh));
-                const float dy = fmaxf(fabsf(hy - byl), fabsf(hy - byh));
-                const float D = fmaf(__builtin_amdgcn_sqrtf(fmaf(dx, dx, dy * dy)), 1.00001f, B * 1e-6f);
-                rec = F4{hx, hy, fmaf(a.gzr, D, a.gzf * B) * 1.00001f, 0.f};
-            }
-        }
-        flagged = __builtin_amdgcn_ballot_w64(lane < nh && rec.w != 0.f);
-        __builtin_amdgcn_wave_barrier();
-        if (lane < kByteHB) recs[lane] = rec;
-        __builtin_amdgcn_wave_barrier();
-    }
-
-    typedef uint64_t u64a1 __attribute__((aligned(1)));   // rows start at any byte
-    auto store = [&](uint8_t *p, uint32_t lo, uint32_t hi, auto partial) {
-        if (!decltype(partial)::value || vmask == 0xffu) {
-            const uint64_t x = (uint64_t)hi << 32 | lo;
-            if (MODE == PV_VOTE_DENSE) {
-                *(u64a1 *)p = x;
-            } else {
-                // KU:125 sets inlier bytes to 1 and leaves the others
-                const uint64_t old = *(const u64a1 *)p;
-                *(u64a1 *)p = (old & ~(x * 0xffu)) | x;
-            }
-        } else if (vmask) {
-            // a row's last pixels (vmask is a prefix): 4 + 2 + 1 bytes at most
-            typedef uint32_t u32a1 __attribute__((aligned(1)));
-            typedef uint16_t u16a1 __attribute__((aligned(1)));
-            const int n = __builtin_popcount(vmask);
-            uint64_t x = (uint64_t)hi << 32 | lo;
-            int o = 0;
-            if (n & 4) {
-                const uint32_t y = (uint32_t)x;
-                if (MODE == PV_VOTE_DENSE) *(u32a1 *)(p + o) = y;
-                else *(u32a1 *)(p + o) = (*(const u32a1 *)(p + o) & ~(y * 0xffu)) | y;
-                x >>= 32;
-                o += 4;
-            }
-            if (n & 2) {
-                const uint16_t y = (uint16_t)x;
-                if (MODE == PV_VOTE_DENSE) *(u16a1 *)(p + o) = y;
-                else *(u16a1 *)(p + o) = (uint16_t)((*(const u16a1 *)(p + o) & ~(y * 0xffu)) | y);
-                x >>= 16;
-                o += 2;
-            }
-            if (n & 1) {
-                const uint8_t y = (uint8_t)x;
-                if (MODE == PV_VOTE_DENSE) p[o] = y;
-                else if (y) p[o] = 1;
-            }
-        }
-    };
-    // inlier bytes from the signs of nz = -z: v_perm's selectors 9 / 11
-    // replicate the sign bit of its second / first operand into a byte, 12 is 0
-    constexpr uint32_t kSgn01 = 0x0c0c0b09u;   // sign(z0) -> b0, sign(z1) -> b1
-    constexpr uint32_t kSgn23 = 0x0b090c0cu;   // sign(z2) -> b2, sign(z3) -> b3
-    auto pack4 = [&](float z0, float z1, float z2, float z3) {
-        const uint32_t p01 = __builtin_amdgcn_perm(__float_as_uint(z1), __float_as_uint(z0), kSgn01);
-        const uint32_t p23 = __builtin_amdgcn_perm(__float_as_uint(z3), __float_as_uint(z2), kSgn23);
-        return (p01 | p23) & 0x01010101u;   // 1 where z > 0 (band pairs fixed below); one v_bitop3
-    };
-    // nz = -z = x' (-tau) + |y'|, and min |nz| for the band check
-    auto zrow = [&](const F4 &rec, float nz[kBytePix]) {
-        float m = 3.0e38f;
-#pragma unroll
-        for (int j = 0; j < kBytePix; ++j) {
-            const float xr = fmaf(fu[j], rec.x, fmaf(fv[j], rec.y, fk1[j]));
-            const float yr = fmaf(fu[j], rec.y, fmaf(-fv[j], rec.x, fk2[j]));
-            nz[j] = fmaf(xr, ntau, fabsf(yr));
-            m = fminf(m, fabsf(nz[j]));
-        }
-        return m;
-    };
-
-    if (tsetup && *tsetup == 0) *tsetup = __builtin_amdgcn_s_memrealtime();   // (trace builds only)
-    // Hot loop: the fast decision of every pair, one 8-byte store per row.
-    // A row with a pair inside the band records which (an 8-bit mask per lane
-    // in LDS) and its word is stored with those bytes as the fast guess
-    // (dense) or left out (OR); the exact pass rewrites just those bytes.
-    // Flagged rows (outside the fast domain) are decided whole by the exact
-    // pass.  Waves holding a partial word (row ends) use byte stores.
-    // Queue this lane's band pairs of row i (bits of bm) in the wave's LDS
-    // queue, decided at the wave's end (fix_queued): a wave prefix of the
-    // per-lane counts (<= 8, four ballots).  False when the queue is full
-    // (entries that fit are still written: deciding a pair twice is harmless,
-    // both give the reference's byte).
-    auto enqueue = [&](uint32_t bm, int i) {
-        const uint32_t n = __builtin_popcount(bm);
-        uint32_t pre = 0, tot = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint64_t m = __builtin_amdgcn_ballot_w64((n >> k) & 1u);
-            pre += (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) << k;
-            tot += (uint32_t)__builtin_popcountll(m) << k;
-        }
-        const uint32_t base = qn;
-        qn = min(base + tot, qcap);
-        uint32_t k = base + pre;
-#pragma unroll
-        for (int j = 0; j < kBytePix; ++j) {
-            if (bm >> j & 1) {
-                // (row in the wave's batch, pixel in the window): 6 + 9 bits
-                if (k < qcap) wq[k] = (uint16_t)(i << 9 | (kBytePix * lane + j));
-                ++k;
-            }
-        }
-        return base + tot <= qcap;
-    };
-    uint64_t dmask = 0;                                 // rows with exact work in this kernel (nh <= 64)
-    uint32_t lof = loff;                                // (loop-carried through the asm below: no copies)
-    auto row = [&](const F4 &rec, int i, uint32_t &lo, uint32_t &hi) {
-        float nz[kBytePix];
-        const float m = zrow(rec, nz);
-        const uint64_t hit = __builtin_amdgcn_ballot_w64(m <= rec.z);   // flagged rows: rec.z = inf
-        lo = pack4(nz[0], nz[1], nz[2], nz[3]);
-        hi = pack4(nz[4], nz[5], nz[6], nz[7]);
-        bool skip = false;
-        if (hit) {
-            dmask |= 1ull << i;
-            if ((flagged >> i) & 1) {
-                skip = MODE != PV_VOTE_DENSE;
-            } else {
-                uint32_t bm = 0;
-#pragma unroll
-                for (int j = 0; j < kBytePix; ++j) bm |= (fabsf(nz[j]) <= rec.z ? 1u : 0u) << j;
-                int io = i;
-                asm volatile("" : "+s"(io));   // address math here, not an induction variable of the hot loop
-                band8[io * kWave + lane] = (uint8_t)bm;
-                if (MODE != PV_VOTE_DENSE) {
-                    lo &= ~((bm & 1u) | (bm & 2u) << 7 | (bm & 4u) << 14 | (bm & 8u) << 21);
-                    hi &= ~((bm >> 4 & 1u) | (bm >> 4 & 2u) << 7 | (bm >> 4 & 4u) << 14 | (bm >> 4 & 8u) << 21);
-                }
-            }
-        }
-        return skip;
-    };
-    using gbyte = __attribute__((address_space(1))) uint8_t;
-    // (the row offset is made opaque so that the address stays a scalar
-    // base + 32-bit lane offset instead of a strength-reduced 64-bit VGPR pointer)
-    auto store_row = [&](int i, uint32_t lo, uint32_t hi, bool skip, auto partial) {
-        uint64_t rp = (uint64_t)(a.out + (obase + rstep * i));
-        rp = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(rp >> 32)) << 32 |
-             (uint32_t)__builtin_amdgcn_readfirstlane((int)rp);
-        gbyte *rowp = (gbyte *)rp;
-        asm volatile("" : "+s"(rowp), "+v"(lof));
-        if (!skip) store((uint8_t *)(rowp + lof), lo, hi, partial);
-    };
-    auto rows = [&](auto partial) {
-        F4 ra = recs[0];
-        int i = 0;
-        for (; i + 1 < nh; i += 2) {
-            const F4 rb = recs[i + 1];
-            if ((i & 7) == 0) prio_by_remaining(rem_after + (uint32_t)(nh - i), wave_total);
-            uint32_t lo0, hi0, lo1, hi1;
-            const bool s0 = row(ra, i, lo0, hi0);
-            ra = recs[min(i + 2, kByteHB - 1)];
-            const bool s1 = row(rb, i + 1, lo1, hi1);
-            store_row(i, lo0, hi0, s0, partial);
-            store_row(i + 1, lo1, hi1, s1, partial);
-        }
-        if (i < nh) {
-            uint32_t lo, hi;
-            const bool sk = row(ra, i, lo, hi);
-            store_row(i, lo, hi, sk, partial);
-        }
-    };
-    if (__builtin_amdgcn_ballot_w64(vmask != 0xffu)) rows(std::true_type{});
-    else rows(std::false_type{});
-
-    // Band rows: their pairs go to k_fix_bytes' queue (outside the hot loop:
-    // the queue's masks and atomics would crowd its registers).
-    {
-        uint64_t m = dmask & ~flagged;
-        while (m) {
-            const int i = __builtin_ctzll(m);
-            m &= m - 1;
-            if (enqueue(band8[i * kWave + lane], i)) dmask &= ~(1ull << i);
-        }
-    }
-    // Exact pass over what is left -- flagged rows, and band rows that found
-    // the queue full: the lane's pixels' reference operands are loaded once
-    // (one memory round trip), then the reference's sequence decides.
-    if (dmask) {
-        float2 ec[kBytePix], ed[kBytePix];
-#pragma unroll
-        for (int j = 0; j < kBytePix; ++j) {
-            const int t = tb + j;
-            ec[j] = ed[j] = make_float2(0.f, 0.f);
-            if (vmask >> j & 1) {
-                if (raw) {
-                    const float4 r = raw[j * kWave + lane];
-                    ec[j] = make_float2(r.x, r.y);
-                    ed[j] = make_float2(r.z, r.w);
-                } else {
-                    ec[j] = *(const float2 *)(a.coords + (int64_t)t * 2);
-                    ed[j] = *(const float2 *)(a.direct + ((int64_t)t * a.vn + v) * 2);
-                }
-            }
-        }
-        while (dmask) {
-            const int i = __builtin_ctzll(dmask);
-            dmask &= dmask - 1;
-            const float2 q = hraw[i];
-            uint8_t *p = a.out + (obase + rstep * i) + loff;
-            if ((flagged >> i) & 1) {
-                uint32_t lo = 0, hi = 0;
-#pragma unroll
-                for (int j = 0; j < kBytePix; ++j) {
-                    const uint32_t bit =
-                        ((vmask >> j & 1) && exact_vote(ed[j].x, ed[j].y, ec[j].x, ec[j].y, q.x, q.y, a.thr)) ? 1u : 0u;
-                    if (j < 4) lo |= bit << (8 * j);
-                    else hi |= bit << (8 * (j - 4));
-                }
-                store(p, lo, hi, std::true_type{});
-            } else {
-                const uint32_t bm = band8[i * kWave + lane];
-#pragma unroll
-                for (int j = 0; j < kBytePix; ++j) {
-                    if (bm >> j & 1) {
-                        const bool e = exact_vote(ed[j].x, ed[j].y, ec[j].x, ec[j].y, q.x, q.y, a.thr);
-                        if (MODE == PV_VOTE_DENSE) p[j] = e ? 1 : 0;
-                        else if (e) p[j] = 1;
-                    }
-                }
-            }
-        }
-    }
-}
-
-// A wave's queued band pairs, decided by the reference's sequence at its
-// end: lane = entry; the operands are the reference's own (c, d, h) -- from
-// the block's raw window in LDS when it is staged (no memory round trip at
-// the wave's end), else loaded, up to 64 pairs in flight at once; the byte
-// goes over the wave's own earlier fast guess (dense, program order) or is
-// set (OR).
-template <int MODE>
-__device__ __forceinline__ void fix_queued(const ByteArgs &a, const uint16_t *wq, uint32_t qn, int v, int w, int h0,
-                                           const float4 *raw, const float2 *hraw) {
-    for (uint32_t k = lane_id(); k < qn; k += kWave) {
-        const uint32_t e = wq[k];
-        const uint32_t i = e >> 9, p = e & (kByteWin - 1);
-        const uint32_t t = (uint32_t)(kByteWin * w) + p;
-        const float2 q = hraw[i];
-        float2 c, d;
-        if (raw) {
-            const float4 r = raw[(p % kBytePix) * kWave + p / kBytePix];
-            c = make_float2(r.x, r.y);
-            d = make_float2(r.z, r.w);
-        } else {
-            c = *(const float2 *)(a.coords + (int64_t)t * 2);
-            d = *(const float2 *)(a.direct + ((int64_t)t * a.vn + v) * 2);
-        }
-        const bool in = exact_vote(d.x, d.y, c.x, c.y, q.x, q.y, a.thr);
-        uint8_t *o = a.out + ((int64_t)(h0 + (int)i) * a.vn + v) * a.tn + t;
-        if (MODE == PV_VOTE_DENSE) *o = in ? 1 : 0;
-        else if (in) *o = 1;
-    }
-}
-
-// One item per wave: (keypoint v, window w, hypothesis group g of kByteHB
-// rows, or of 16 rows in a quarter block of the balanced grid), g fastest;
-// a wave beyond the items exits.
-template <int MODE, int WPB>
-__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(5, 8))) void k_vote_bytes(ByteArgs a) {
-    __shared__ F4 recs_all[WPB][kByteHB];
-    __shared__ alignas(16) uint8_t band_all[WPB][kByteHB * kWave];   // per deferred row: each lane's band-pair mask
-    __shared__ uint16_t queue_all[WPB][kQueuePerWave];     // per wave: queued band pairs (row, pixel)
-    __shared__ float2 hraw_all[WPB][kByteHB];              // per wave: its rows' hypotheses
-    __shared__ float4 raw_win[WPB == 4 ? kByteWin : 1];    // block-staged window: (c, d) as given
-    __shared__ float4 win_part[WPB];                       // per wave: its pixels' bounds (staging)
-    __shared__ int win_exo[WPB];
-    F4 *recs = recs_all[threadIdx.x / 64];
-    uint8_t *band8 = band_all[threadIdx.x / 64];
-    uint16_t *wq = queue_all[threadIdx.x / 64];
-    float2 *hraw = hraw_all[threadIdx.x / 64];
-    // setup at the top issue priority, above every hot loop (whose waves
-    // rank 0..2 by the rows they have left, prio_by_remaining): a wave still
-    // in its setup would otherwise wait for them -- and then finish last
-    __builtin_amdgcn_s_setprio(3);
-    int blk = (int)blockIdx.x;
-#ifdef PVVOTE_TRACE_U1
-    const uint64_t t_start = __builtin_amdgcn_s_memrealtime();
-    uint64_t t_setup = 0;
-    uint64_t *tsetup = &t_setup;
-#else
-    uint64_t *tsetup = nullptr;
-#endif
-    // Every load of the wave is issued at the launch's start, in one round
-    // trip: the item's hypotheses, and the window's pixels.  With the
-    // hypothesis groups in fours (hn a multiple of 256) a block's four items
-    // share (v, w): the block stages the window's pixels in LDS once (the
-    // band-mask area, free until the hot loop) instead of four times.
-    const bool shared = WPB == 4 && a.nhg % 4 == 0;
-    int wave, v, w, h0, nh;
-    if (WPB == 4 && a.bal_nt > 0) {
-        // CU-balanced grid (shared staging only): the bal_t full blocks (64
-        // rows per wave) are a multiple of the CU count; the remaining units
-        // are split four ways into quarter blocks (16 rows per wave),
-        // dispatched after the full ones -- at most one beside a CU's full
-        // blocks, so every CU carries the same rows to within a quarter block
-        // instead of a whole fifth block on some.  Each XCD (blocks i, i + 8,
-        // ... under round-robin dispatch) takes a contiguous share of both
-        // kinds, full ones first.  (Speed only: any placement is correct.)
-        const int x = blk % 8, k = blk / 8;
-        int u, part = -1;
-        if (k < a.bal_tnx) {
-            u = x * a.bal_tnx + k;
-            if (u >= a.bal_t) return;                     // (whole blocks)
-        } else {
-            const int i = x * a.bal_ttx + (k - a.bal_tnx);
-            if (i >= a.bal_nt) return;
-            u = a.bal_t + i / 4;
-            part = i % 4;
-        }
-        const int G = a.nhg / 4, q = (int)(threadIdx.x / 64);
-        const int gq = u % G, rest = u / G;
-        v = rest % a.vn;
-        w = (rest / a.vn + a.nwin - 1) % a.nwin;
-        h0 = part < 0 ? gq * 4 * kByteHB + q * kByteHB : gq * 4 * kByteHB + part * kByteHB + q * (kByteHB / 4);
-        nh = part < 0 ? kByteHB : kByteHB / 4;
-        wave = uniform(blk * 4 + q);
-    } else {
-        if (a.xcd) {
-            // blocks i, i + 8, ... run on one XCD (round-robin dispatch; speed
-            // only, nothing depends on it): give each XCD a contiguous range of
-            // items, whose windows' pixels its L2 then fetches once
-            const int per = (int)gridDim.x / 8;   // (the host pads the grid to a multiple of 8)
-            blk = (blk % 8) * per + blk / 8;
-        }
-        wave = uniform(blk * WPB + (int)(threadIdx.x / 64));
-        const uint32_t nitems = (uint32_t)a.vn * a.nwin * a.nhg;   // < 2^31 (host-checked)
-        // (shared: nitems is a multiple of 4, every wave of a block has an item)
-        if ((uint32_t)wave >= nitems) return;
-        // items (w, v, g), g fastest: a window's items are adjacent; the last
-        // (partial) window first, so that its slower byte-store rows are not the
-        // launch's tail
-        const uint32_t g = (uint32_t)wave % a.nhg, rest = (uint32_t)wave / a.nhg;
-        v = (int)(rest % (uint32_t)a.vn);
-        w = (int)((rest / (uint32_t)a.vn + (uint32_t)a.nwin - 1) % (uint32_t)a.nwin);
-        h0 = (int)g * kByteHB;
-        nh = min(kByteHB, a.hn - h0);
-    }
-    v = uniform(v); w = uniform(w); h0 = uniform(h0); nh = uniform(nh);
-    float2 hq = make_float2(0.f, 0.f);
-    if (lane_id() < nh) hq = *(const float2 *)(a.hypo + ((int64_t)(h0 + lane_id()) * a.vn + v) * 2);
-    if (lane_id() < kByteHB) hraw[lane_id()] = hq;
-    const float4 *stage = nullptr, *raw = nullptr;
-    WinInfo wi{};
-    if (WPB == 4 && shared) {
-        // the block's window, once: raw (c, d) for the exact decisions, the
-        // fast operands (ux, uy, -k1, -k2) relative to the window's origin
-        // (the floor of its first pixel), and the voting pixels' bounds
-        float4 *st = (float4 *)&band_all[0][0];
-        constexpr int kPer = kByteWin / 256;   // pixels per thread; loads first, then the operands
-        const int t0 = kByteWin * w;
-        float2 c[kPer], d[kPer];
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-            const int t = t0 + k * 256 + (int)threadIdx.x;
-            if (t < a.tn) { c[k] = api_coords(a, t); d[k] = api_direct(a, t, v); }
-        }
-        const float2 c0 = api_coords(a, t0);
-        const bool obad = !(isfinite(c0.x) && isfinite(c0.y));
-        const float ox = obad ? 0.f : floorf(c0.x), oy = obad ? 0.f : floorf(c0.y);
-        float xl = 3.0e38f, xh = -3.0e38f, yl = 3.0e38f, yh = -3.0e38f;
-        bool exo = false;
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-            const int t = t0 + k * 256 + (int)threadIdx.x;
-            // lane-interleaved: lane l's pixel j (k = 8l + j) at j * 64 + l, so
-            // that each of the waves' eight reads is 64 consecutive float4
-            const int kk = k * 256 + (int)threadIdx.x;
-            if (t < a.tn) {
-                const float4 q = api_pixel(c[k], d[k]);
-                const bool ok = q.x != 0.f || q.y != 0.f;   // votes at all (NaN: outside the fast domain)
-                exo |= q.x != q.x;
-                const float cx = q.z - ox, cy = q.w - oy;
-                float4 f = make_float4(0.f, 0.f, -1.0e30f, 0.f);   // never votes: -z = 1e30 tau
-                if (ok) {
-                    f = make_float4(q.x, q.y, -fmaf(q.x, cx, q.y * cy), -fmaf(q.x, cy, -(q.y * cx)));
-                    xl = fminf(xl, cx); xh = fmaxf(xh, cx);
-                    yl = fminf(yl, cy); yh = fmaxf(yh, cy);
-                }
-                st[(kk % kBytePix) * kWave + kk / kBytePix] = f;
-                raw_win[(kk % kBytePix) * kWave + kk / kBytePix] = make_float4(c[k].x, c[k].y, d[k].x, d[k].y);
-            }
-        }
-        xl = wave_min(xl); xh = wave_max(xh);
-        yl = wave_min(yl); yh = wave_max(yh);
-        const bool wexo = __builtin_amdgcn_ballot_w64(exo) != 0;
-        if (lane_id() == 0) {
-            win_part[threadIdx.x / 64] = make_float4(xl, xh, yl, yh);
-            win_exo[threadIdx.x / 64] = wexo;
-        }
-        __syncthreads();
-        float4 p = win_part[0];
-        int ex = win_exo[0];
-#pragma unroll
-        for (int k = 1; k < 4; ++k) {
-            const float4 q = win_part[k];
-            p.x = fminf(p.x, q.x); p.y = fmaxf(p.y, q.y);
-            p.z = fminf(p.z, q.z); p.w = fmaxf(p.w, q.w);
-            ex |= win_exo[k];
-        }
-        wi.slow = ex | obad;
-        wi.ox = ox; wi.oy = oy;
-        if (p.x <= p.y) {   // some pixel votes
-            wi.bxl = p.x; wi.bxh = p.y; wi.byl = p.z; wi.byh = p.w;
-            const float ax = fmaxf(-p.x, p.y), ay = fmaxf(-p.z, p.w);
-            wi.Rw = __builtin_amdgcn_sqrtf(fmaf(ax, ax, ay * ay)) * 1.00001f;
-        }
-        stage = st;
-        raw = raw_win;
-    }
-#ifdef PVVOTE_TRACE_U1
-    const uint64_t t_staged = __builtin_amdgcn_s_memrealtime();
-#endif
-    uint32_t qn = 0;
-    vote_bytes_seg<MODE>(a, recs, band8, uniform(v), uniform(w), uniform(h0), uniform(nh), 0u, (uint32_t)nh, wq, qn,
-                         tsetup, stage, hq, raw, hraw, &wi);
-#ifdef PVVOTE_TRACE_U1
-    const uint64_t t_first = __builtin_amdgcn_s_memrealtime();
-#endif
-    __builtin_amdgcn_wave_barrier();
-    fix_queued<MODE>(a, wq, qn, v, w, h0, raw, hraw);
-#ifdef PVVOTE_TRACE_U1
-    if (g_btrace && lane_id() == 0) {
-        g_btrace[wave * 8] = t_start;
-        g_btrace[wave * 8 + 1] = t_first;
-        g_btrace[wave * 8 + 2] = __builtin_amdgcn_s_memrealtime();
-        g_btrace[wave * 8 + 3] = t_setup;
-        g_btrace[wave * 8 + 4] = t_staged;
-        uint32_t hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        g_btrace[wave * 8 + 5] = ((uint64_t)xcc << 32) | hw;
-    }
-#endif
-}
-
-// test hook of the matrix-core sums the vote kernel's error bound rests on
-// (pv_debug_mfma_sums): tile i = A [32][8] fp16 x B [8][32] fp16 -> D
-// [32][32] f32 by the instruction k_vote_mfma issues, with a zero accumulator
-// as there; lane l holds A[l & 31][4 (l >> 5) + j] and B[4 (l >> 5) + j][l & 31]
-__global__ __launch_bounds__(64) void k_debug_mfma_sums(const uint16_t *A, const uint16_t *B, float *D) {
-    const int l = threadIdx.x, r = l & 31, h = l >> 5;
-    const uint16_t *At = A + (int64_t)blockIdx.x * 256, *Bt = B + (int64_t)blockIdx.x * 256;
-    h4f a, b;
-    for (int j = 0; j < 4; ++j) {
-        a[j] = __builtin_bit_cast(_Float16, At[r * 8 + 4 * h + j]);
-        b[j] = __builtin_bit_cast(_Float16, Bt[(4 * h + j) * 32 + r]);
-    }
-    const f32x16 zero = {};
-    const f32x16 c = __builtin_amdgcn_mfma_f32_32x32x8f16(a, b, zero, 0, 0, 0);
-    float *Dt = D + (int64_t)blockIdx.x * 1024;
-    for (int i = 0; i < 16; ++i) Dt[((i & 3) + 8 * (i >> 2) + 4 * h) * 32 + r] = c[i];
-}
-
-// test hook of wave_min / wave_max (pv_debug_wave_minmax)
-__global__ __launch_bounds__(64) void k_debug_minmax(const float *in, float *out) {
-    const float x = in[blockIdx.x * 64 + threadIdx.x];
-    const float mn = wave_min(x), mx = wave_max(x);
-    // every lane must hold the result
-    const bool agree = __builtin_amdgcn_ballot_w64(mn != bcast(mn, 0) || mx != bcast(mx, 0)) == 0;
-    if (threadIdx.x == 0) {
-        out[2 * blockIdx.x] = agree ? mn : __builtin_nanf("");
-        out[2 * blockIdx.x + 1] = agree ? mx : __builtin_nanf("");
-    }
-}
-
-// KU:170-229
-__global__ __launch_bounds__(256) void k_generate_vp(const float *direct, const float *coords, const int32_t *idxs,
-                                                     float *hypo, int tn, int vn, int hn) {
-    int hv = blockIdx.x * 256 + threadIdx.x;
-    if (hv >= hn * vn) return;
-    int hi = hv / vn, vi = hv - hi * vn;
-    int id0 = idxs[hi * vn * 2 + vi * 2], id1 = idxs[hi * vn * 2 + vi * 2 + 1];
-    float x = 0.f, y = 0.f, z = 0.f;
-    if (id0 >= 0 && id0 < tn && id1 >= 0 && id1 < tn) {
-        float dx0 = direct[id0 * vn * 2 + vi * 2], dy0 = direct[id0 * vn * 2 + vi * 2 + 1];
-        float cx0 = coords[id0 * 2], cy0 = coords[id0 * 2 + 1];
-        float dx1 = direct[id1 * vn * 2 + vi * 2], dy1 = direct[id1 * vn * 2 + vi * 2 + 1];
-        float cx1 = coords[id1 * 2], cy1 = coords[id1 * 2 + 1];
-        float lx0 = dy0, ly0 = -dx0, lz0 = cy0 * dx0 - cx0 * dy0;
-        float lx1 = dy1, ly1 = -dx1, lz1 = cy1 * dx1 - cx1 * dy1;
-        x = ly0 * lz1 - lz0 * ly1;
-        y = lz0 * lx1 - lx0 * lz1;
-        z = lx0 * ly1 - ly0 * lx1;
-        float vx0 = dx0 * (x - z * cx0), vx1 = dx1 * (x - z * cx1);
-        float vy0 = dy0 * (y - z * cy0), vy1 = dy1 * (y - z * cy1);
-        if (vx0 < 0 && vx1 < 0 && vy0 < 0 && vy1 < 0) { z = -z; x = -x; y = -y; }
-        if (vx0 * vx1 < 0 || vy0 * vy1 < 0) { x = 0.f; y = 0.f; z = 0.f; }
-    }
-    hypo[hi * vn * 3 + vi * 3] = x;
-    hypo[hi * vn * 3 + vi * 3 + 1] = y;
-    hypo[hi * vn * 3 + vi * 3 + 2] = z;
-}
-
-// KU:268-310
-__global__ __launch_bounds__(256) void k_vote_vp(const float *direct, const float *coords, const float *hypo,
-                                                 uint8_t *inliers, int tn, int vn, int hn, float thr) {
-    int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    int64_t tot = (int64_t)hn * vn * tn;
-    if (gid >= tot) return;
-    int ti = (int)(gid % tn);
-    int vi = (int)((gid / tn) % vn);
-    int hi = (int)(gid / ((int64_t)tn * vn));
-    float cx = coords[ti * 2], cy = coords[ti * 2 + 1];
-    float hx = hypo[(hi * vn + vi) * 3], hy = hypo[(hi * vn + vi) * 3 + 1], hz = hypo[(hi * vn + vi) * 3 + 2];
-    float ddx = direct[(int64_t)ti * vn * 2 + vi * 2], ddy = direct[(int64_t)ti * vn * 2 + vi * 2 + 1];
-    float fx = hx - cx * hz, fy = hy - cy * hz;
-    float n1 = sqrtf(ddx * ddx + ddy * ddy);
-    float n2 = sqrtf(fx * fx + fy * fy);
-    if (below_1e6(n1) || below_1e6(n2)) return;
-    float ad = (ddx * fx + ddy * fy) / (n1 * n2);
-    float vx = fx * ddx, vy = fy * ddy;
-    if (vx < 0 || vy < 0) return;
-    if (fabsf(ad) > thr) inliers[gid] = 1;
-}
-
-
-// Constants of the rotated-frame test (DESIGN.md "Exactness of the fast vote
-// test"): tau = sqrt(1-thr^2)/thr; band = gzf * B + gzr * D with
-// B >= |h - o| + |c - o| and D >= |h - c|:
-//   gzf = 2 * (9 tau + 8) * 2^-24   the fast path's rounding (7 tau + 6, plus
-//                                   2 (tau + 1) for a rounded c - o when the
-//                                   coordinates are not integers)
-//   gzr = 2 * 9.5 (tau + 1/tau) * 2^-24   the reference's 8-ulp cosine error
-//                                   (+1.5 ulp for its rounded d) mapped
-//                                   through dz/dcos = |d| (tau + 1/tau)
-// both with 2x margin.
-void fast_constants(float thr, VoteArgs *va) {
-    va->thr = thr;
-    const double t = (double)thr;
-    if (t >= 0.05 && t <= 0.999999) {
-        const double tau = sqrt(1.0 - t * t) / t;
-        const double u = 1.0 / 16777216.0;
-        va->tau = (float)tau;
-        va->gzf = (float)(2.0 * (9.0 * tau + 8.0) * u * 1.0001);
-        va->gzr = (float)(2.0 * 9.5 * (tau + 1.0 / tau) * u * 1.0001);
-        va->fast = 1;
-    } else {   // outside the derivation's range: every pair takes the exact sequence
-        va->tau = 0.f;
-        va->gzf = 0.f;
-        va->gzr = 0.f;
-        va->fast = 0;
-    }
-}
-
 // The matrix-core vote (k_vote_mfma): its own fast-path constant (DESIGN.md
 // section 5a): per form F the error is <= u |a_F| (37.7 + [X] 2 sqrt 2 tau) B
 // (h', c' and b roundings 5.7, fp16 splits 12, b split 4, the matrix core's
@@ -2128,7 +1312,7 @@ void fast_constants(float thr, VoteArgs *va) {
 // 14 u sum|terms|, +1 u for the final rounding, +1 u margin; tested with
 // crafted cancellation sums, test_mfma_sum_error_bound), z = X - |Y| adds
 // u (tau + 1) B:
-//   gzm = 2 (41.5 tau + 38.7) 2^-24 (2x margin);  gzr as above.
+//   gzm = 2 (41.5 tau + 38.7) 2^-24 (2x margin);  gzr is fast_constants'.
 float mfma_gz(float tau) { return (float)(2.0 * (41.5 * (double)tau + 38.7) / 16777216.0 * 1.0001); }
 
 // persistent vote grid: every block resident at once (the occupancy limit of
@@ -2154,17 +1338,12 @@ uint64_t *g_vote_trace = nullptr;   // trace builds only (pv_debug_set_vote_trac
 // comments and DESIGN.md section 7; the variants measured and removed are in
 // DESIGN.md's appendix "Removed variants".
 
-// Test hooks, not for production (not in pvvote.h, set only by explicit calls
+// Test hook, not for production (not in pvvote.h, set only by explicit calls
 // between launches, never during a capture): which fused vote/count kernel
 // the pipeline runs (pv_debug_set_vote_kernel: the tests check both in one
-// process) and the byte kernel's band-queue capacity (pv_debug_set_bytes_mode
-// 4: a queue of one entry, so the in-kernel exact pass runs).  Atomic, relaxed:
-// concurrent caller threads read them on every call.
+// process).  Atomic, relaxed: concurrent caller threads read it on every call.
 std::atomic<int> g_vote_kernel{0};   // 0: k_vote_mfma (hn a multiple of 512), 1: k_vote_count
-std::atomic<int> g_bytes_dbg{0};
 bool vote_old() { return g_vote_kernel.load(std::memory_order_relaxed) == 1; }
-// does front_half pre-generate the hypotheses (k_hyp_gen, keypoint-major in w.hypv)?
-bool hyp_pregen_used(int nh) { return ((nh + kGroup - 1) / kGroup) % 4 == 0 && !vote_old(); }
 
 template <bool PREPPED>
 void launch_vote(const VoteArgs &va, int64_t pixel_steps, hipStream_t s) {
@@ -2200,294 +1379,62 @@ void launch_vote(const VoteArgs &va, int64_t pixel_steps, hipStream_t s) {
             <<<vote_grid_steps(pixel_steps, (const void *)k_vote_count<PREPPED, false>), 256, 0, s>>>(va);
 }
 
-int check_desc(const pv_image_desc *img) {
-    if (!img || !img->mask || !img->vertex) return PV_EINVAL;
-    if (img->b <= 0 || img->H <= 0 || img->W <= 0 || img->vn <= 0 || img->vn > 64) return PV_EINVAL;
-    if (img->H > 65535 || img->W > 65535) return PV_EINVAL;   // pixel centres pack into 16 bits
-    if (img->mask_kind < PV_MASK_I64 || img->mask_kind > PV_MASK_SEG_F16) return PV_EINVAL;
-    if (img->vertex_kind != PV_VERTEX_F32 && img->vertex_kind != PV_VERTEX_F16) return PV_EINVAL;
-    if (img->ncls < 0 || img->ncls > 64) return PV_EINVAL;
-    if ((int64_t)img->b * std::max(img->ncls, 1) > INT32_MAX) return PV_EINVAL;
-    return PV_OK;
-}
-
-// the images the pipeline's stages after k_label_count see: one per (image,
-// class) of a multi-object call (the virtual image bv = bi * ncls + c)
-int pipeline_images(const pv_image_desc *img) { return img->b * std::max(img->ncls, 1); }
-
-// The mask and vertex views of a call's images.  extent is left 0: front_half
-// works it out (the compaction's buffer loads need it), the motion path never
-// reads it.
-void image_views(const pv_image_desc *img, MaskView *m, VertexView *vx) {
-    *m = MaskView{img->mask, img->mask_strides[0], img->mask_strides[1], img->mask_strides[2], img->mask_strides[3]};
-    vx->p = img->vertex;
-    vx->kind = img->vertex_kind;
-    for (int i = 0; i < 5; ++i) vx->s[i] = img->vertex_strides[i];
-    vx->extent = 0;
-    vx->ncls = img->ncls;
-    vx->cs = (int64_t)img->vn * img->vertex_strides[3];
-}
-
-// The vote kernels index their work in 32 bits: the vote units of one image
-// if every pixel were foreground (0: too many, the call is refused) ...
-int64_t vote_units_per_image(int vn, int nh, int64_t P) {
-    const int64_t per_img = (int64_t)vn * ((nh + kGroup - 1) / kGroup) * P;
-    return per_img >= (1ll << 31) ? 0 : per_img;
-}
-// ... and the images per vote launch such that this upper bound stays < 2^31
-int images_per_vote_launch(int b, int64_t per_img) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>(b, ((1ll << 31) - 1) / per_img));
-}
-// the hypotheses by k_compact's first blocks (compact_hyp) instead of a k_hyp_gen launch
-bool hyp_fused(int nh, int nblk) { return hyp_pregen_used(nh) && nblk <= kHypMaxChunks; }
-
-// compaction + hypotheses + fused vote/count, shared by v3 and EVD
-int front_half(const pv_image_desc *img, const pv_vote_params *prm, int nh, bool evd, const Workspace &w,
-               const pv_v3_diag &dg, hipStream_t s) {
-    const int b = pipeline_images(img), H = img->H, W = img->W, vn = img->vn;
-    const int64_t P = (int64_t)H * W;
-    const int nblk = (int)((P + kCompactChunk - 1) / kCompactChunk);
-    CompactArgs ca;
-    ca.ncls = img->ncls;
-    ca.mask_kind = img->mask_kind;
-    ca.evd = evd;
-    image_views(img, &ca.m, &ca.vx);
-    {   // bytes one image's view spans (the compaction's buffer-load range)
-        const int64_t es = img->vertex_kind == PV_VERTEX_F32 ? 4 : 2;
-        int64_t hi = 0;
-        const int64_t dims[5] = {1, H, W, (int64_t)vn * std::max(img->ncls, 1), 2};   // the whole image view
-        for (int i = 1; i < 5; ++i) {
-            if (ca.vx.s[i] < 0) return PV_EINVAL;
-            hi += (dims[i] - 1) * ca.vx.s[i];
-        }
-        if ((hi + 1) * es > INT32_MAX) return PV_EINVAL;
-        ca.vx.extent = (int32_t)((hi + 1) * es);
-    }
-    ca.b = b; ca.H = H; ca.W = W; ca.vn = vn; ca.nblk = nblk;
-    ca.min_num = prm->min_num; ca.max_num = prm->max_num;
-    ca.seed = mix64(prm->seed ^ 0xd1b54a32d192ed03ull);
-    ca.keep = prm->keep;
-    ca.ws = w;
-    ca.s = s;
-    const int64_t per_img = vote_units_per_image(vn, nh, P);
-    if (!per_img) return PV_EINVAL;
-    const bool hfuse = hyp_fused(nh, nblk) && !(g_abl & 2);
-    ca.hg = HypGen{};
-    if (hfuse) {
-        ca.hg.nhb = (int)(((int64_t)nh * vn + 255) / 256);
-        ca.hg.nh = nh; ca.hg.vn = vn; ca.hg.min_num = prm->min_num; ca.hg.max_num = prm->max_num;
-        ca.hg.seed = mix64(prm->seed); ca.hg.kseed = ca.seed;
-        ca.hg.idxs = prm->idxs; ca.hg.keep = prm->keep;
-        ca.hg.hyp_out = w.hyp; ca.hg.hypv_out = w.hypv; ca.hg.diag_hyp = dg.hyp;
-        ca.hg.keptbits = w.keptbits;
-    }
-    int r = compact(ca);
-    if (r) return r;
-    if (dg.ev_compact_end) {
-        hipError_t e = hipEventRecord((hipEvent_t)dg.ev_compact_end, s);
-        if (e != hipSuccess) return rc(e);
-    }
-    VoteArgs va{};
-    va.pex = w.pex; va.P = (int32_t)P;
-    va.hyp = nullptr;
-    va.hyp_out = w.hyp; va.diag_hyp = dg.hyp;
-    va.idxs = prm->idxs; va.seed = mix64(prm->seed);
-    va.counts = w.counts; va.cnt_bs = vn * nh; va.cnt_v = nh; va.cnt_h = 1;
-    va.tn_dev = w.tn; va.tn_host = 0;
-    va.b = b; va.vn = vn; va.nh = nh; va.hgn = (nh + kGroup - 1) / kGroup;
-    fast_constants(prm->inlier_thresh, &va);
-#ifdef PVV_TRACE
-    va.trace = g_vote_trace;
-#endif
-    // the vote kernel generates the hypotheses itself (item_hyp in its
-    // prologue, overlapped with its first pixel loads) and stores them in
-    // the reference layout; by default (hyp_pregen) one k_hyp_gen launch makes
-    // them first and the vote kernel (k_vote_mfma) reads them keypoint-major
-    if (hyp_pregen_used(nh)) {
-        va.hypv_out = w.hypv;
-        const int64_t nt = (int64_t)b * nh * vn;
-        if (hfuse) {
-        } else if (!(g_abl & 2)) k_hyp_gen<<<(unsigned)((nt + 255) / 256), 256, 0, s>>>(va);
-#ifdef PVV_PROFILE
-        else if (g_abl & 32) k_abl_empty<<<1, 64, 0, s>>>(0);
-#endif
-        if ((r = last())) return r;
-        va.hyp = w.hypv; va.hyp_sb = (int64_t)vn * nh; va.hyp_sv = nh; va.hyp_sh = 1;
-    }
-    if (dg.ev_vote_begin) {
-        hipError_t e = hipEventRecord((hipEvent_t)dg.ev_vote_begin, s);
-        if (e != hipSuccess) return rc(e);
-    }
-    const int chunk = images_per_vote_launch(b, per_img);
-    for (int b0 = 0; b0 < b; b0 += chunk) {
-        VoteArgs vc = va;
-        const int nb = std::min(chunk, b - b0);
-        vc.b = nb;
-        vc.b0 = b0;
-        vc.pex += (int64_t)b0 * vn * P;
-        vc.hyp_out += (int64_t)b0 * nh * vn;
-        if (vc.hyp) vc.hyp += (int64_t)b0 * nh * vn;
-        if (vc.diag_hyp) vc.diag_hyp += (int64_t)b0 * nh * vn * 2;
-        if (vc.idxs) vc.idxs += (int64_t)b0 * nh * vn * 2;
-        vc.counts += (int64_t)b0 * va.cnt_bs;
-        vc.tn_dev += b0;
-        if (!(g_abl & 4)) launch_vote<true>(vc, nb * per_img, s);
-        if ((r = last())) return r;
-    }
-    if (dg.ev_vote_end) return rc(hipEventRecord((hipEvent_t)dg.ev_vote_end, s));
-    return PV_OK;
-}
-
 }  // namespace
 
+namespace pvv __attribute__((visibility("hidden"))) {
 
-// ==========================================================================
-// C ABI
-// ==========================================================================
-extern "C" {
+// Constants of the rotated-frame test (DESIGN.md "Exactness of the fast vote
+// test"): tau = sqrt(1-thr^2)/thr; band = gzf * B + gzr * D with
+// B >= |h - o| + |c - o| and D >= |h - c|:
+//   gzf = 2 * (9 tau + 8) * 2^-24   the fast path's rounding (7 tau + 6, plus
+//                                   2 (tau + 1) for a rounded c - o when the
+//                                   coordinates are not integers)
+//   gzr = 2 * 9.5 (tau + 1/tau) * 2^-24   the reference's 8-ulp cosine error
+//                                   (+1.5 ulp for its rounded d) mapped
+//                                   through dz/dcos = |d| (tau + 1/tau)
+// both with 2x margin.
+void fast_constants(float thr, VoteArgs *va) {
+    va->thr = thr;
+    const double t = (double)thr;
+    if (t >= 0.05 && t <= 0.999999) {
+        const double tau = sqrt(1.0 - t * t) / t;
+        const double u = 1.0 / 16777216.0;
+        va->tau = (float)tau;
+        va->gzf = (float)(2.0 * (9.0 * tau + 8.0) * u * 1.0001);
+        va->gzr = (float)(2.0 * 9.5 * (tau + 1.0 / tau) * u * 1.0001);
+        va->fast = 1;
+    } else {   // outside the derivation's range: every pair takes the exact sequence
+        va->tau = 0.f;
+        va->gzf = 0.f;
+        va->gzr = 0.f;
+        va->fast = 0;
+    }
+}
 
-const char *pv_version(void) { return PV_VERSION; }
+// does front_half pre-generate the hypotheses (k_hyp_gen, keypoint-major in w.hypv)?
+bool hyp_pregen_used(int nh) { return ((nh + kGroup - 1) / kGroup) % 4 == 0 && !vote_old(); }
 
-#define PVV_STR2(x) #x
-#define PVV_STR(x) PVV_STR2(x)
-const char *pv_build_config(void) {
-    // (band, rw, hypgen, hypfuse, fg_cpb, compact_skip: switches since fixed, kept
-    // as literals so that bench records stay comparable across rounds)
-    return "vote=k_vote_mfma(bpc=" PVV_STR(PVV_VM_BPC) ",wpe=" PVV_STR(PVM_WPE) ",chunk=" PVV_STR(PVM_CHUNK) ",queue=" PVV_STR(PVM_QUEUE) ",band=2,rw=0/0/0)"
-           " hypgen=1 hypfuse=1"
-           " refine=" PVV_STR(PVV_REFINE_NJ) "x" PVV_STR(PVV_REFINE_T)
-           " fg_cpb=1/8 compact_skip=1"
-           " bytes=k_vote_bytes(rows=" PVV_STR(PVV_BYTE_HB) ",xcd=" PVV_STR(PVV_BYTES_XCD) ",bal=" PVV_STR(PVV_BYTES_BAL) ")"
-#ifdef PVV_TRACE
-           " TRACE"
-#endif
+void launch_hyp_gen(const VoteArgs &va, hipStream_t s) {
+    const int64_t nt = (int64_t)va.b * va.nh * va.vn;
+    if (!(g_abl & 2)) k_hyp_gen<<<(unsigned)((nt + 255) / 256), 256, 0, s>>>(va);
 #ifdef PVV_PROFILE
-           " PROFILE"
+    else if (g_abl & 32) k_abl_empty<<<1, 64, 0, s>>>(0);
 #endif
-        ;
 }
 
-const char *pv_error_string(int code) {
-    switch (code) {
-    case PV_OK: return "ok";
-    case PV_EINVAL: return "invalid argument";
-    case PV_EWORKSPACE: return "workspace missing or too small";
-    case PV_EALIGN: return "misaligned pointer";
-    default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown error";
-    }
+void launch_pipeline_vote(const VoteArgs &va, int64_t pixel_steps, hipStream_t s) {
+#ifdef PVV_TRACE
+    VoteArgs vt = va;
+    vt.trace = g_vote_trace;
+    launch_vote<true>(vt, pixel_steps, s);
+#else
+    launch_vote<true>(va, pixel_steps, s);
+#endif
 }
 
-int pv_device_arch(char *buf, int len) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return rc(e);
-    hipDeviceProp_t prop;
-    e = hipGetDeviceProperties(&prop, dev);
-    if (e != hipSuccess) return rc(e);
-    if (buf && len > 0) {
-        strncpy(buf, prop.gcnArchName, (size_t)len - 1);
-        buf[len - 1] = 0;
-    }
-    return PV_OK;
-}
+}  // namespace pvv
 
-int pv_stream_create(int32_t priority, pv_stream_t *out) {
-    if (!out) return PV_EINVAL;
-    hipStream_t s = nullptr;
-    const hipError_t e = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority);
-    if (e != hipSuccess) return rc(e);
-    *out = (pv_stream_t)s;
-    return PV_OK;
-}
-
-int pv_stream_destroy(pv_stream_t stream) {
-    if (!stream) return PV_EINVAL;
-    return rc(hipStreamDestroy((hipStream_t)stream));
-}
-
-int pv_stream_capture_id(pv_stream_t stream, uint64_t *id) {
-    if (!id) return PV_EINVAL;
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    unsigned long long cid = 0;
-    const hipError_t e = hipStreamGetCaptureInfo((hipStream_t)stream, &st, &cid);
-    if (e != hipSuccess) return rc(e);
-    *id = st == hipStreamCaptureStatusActive ? (uint64_t)cid : 0;
-    return PV_OK;
-}
-
-int pv_generate_hypothesis(const float *direct, const float *coords, const int32_t *idxs, float *hypo, int32_t tn,
-                           int32_t vn, int32_t hn, pv_stream_t stream) {
-    if (!direct || !coords || !idxs || !hypo || tn <= 0 || vn <= 0 || hn < 0) return PV_EINVAL;
-    if (hn == 0) return PV_OK;
-    int64_t n = (int64_t)hn * vn;
-    k_generate_api<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(direct, coords, idxs, hypo, tn, vn,
-                                                                                  hn);
-    return last();
-}
-
-
-int pv_voting_for_hypothesis(const float *direct, const float *coords, const float *hypo, uint8_t *inliers,
-                             int32_t tn, int32_t vn, int32_t hn, float inlier_thresh, int32_t mode,
-                             pv_stream_t stream) {
-    if (!direct || !coords || !hypo || !inliers || tn < 0 || vn <= 0 || hn < 0) return PV_EINVAL;
-    if (mode != PV_VOTE_OR && mode != PV_VOTE_DENSE) return PV_EINVAL;
-    if (tn == 0 || hn == 0) return PV_OK;
-    VoteArgs fc{};
-    fast_constants(inlier_thresh, &fc);
-    ByteArgs ba{};
-    ba.direct = direct; ba.coords = coords; ba.hypo = hypo; ba.out = inliers;
-    ba.tn = tn; ba.vn = vn; ba.hn = hn;
-    ba.fast = fc.fast; ba.thr = fc.thr; ba.tau = fc.tau; ba.gzf = fc.gzf; ba.gzr = fc.gzr;
-    ba.nwin = (tn + kByteWin - 1) / kByteWin;
-    ba.nhg = (hn + kByteHB - 1) / kByteHB;
-    ba.dbg = g_bytes_dbg.load(std::memory_order_relaxed);
-    const int64_t items = (int64_t)vn * ba.nwin * ba.nhg;
-    if (items >= (1ll << 31)) return PV_EINVAL;   // the kernel's 32-bit item index
-    // one launch, no scratch: the operands are made where the blocks stage them
-    unsigned grid = (unsigned)((items + 3) / 4);
-    ba.xcd = PVV_BYTES_XCD;
-    if (ba.xcd) grid = (grid + 7) / 8 * 8;
-    if (PVV_BYTES_BAL && ba.nhg % 4 == 0 && ba.xcd) {
-        // CU-balanced grid: full blocks a multiple of the CU count, the rest
-        // as quarter blocks, when that leaves at most one quarter block per CU
-        // beside four full ones (one resident round; see k_vote_bytes)
-        const int64_t units = items / 4, cus = cu_count();
-        const int64_t T = units / cus * cus, E = units - T;
-        if (T > 0 && T <= 4 * cus && E > 0 && 4 * E <= cus) {
-            ba.bal_t = (int)T;
-            ba.bal_nt = (int)(4 * E);
-            ba.bal_tnx = (int)((T + 7) / 8);
-            ba.bal_ttx = (int)((4 * E + 7) / 8);
-            grid = (unsigned)(8 * (ba.bal_tnx + ba.bal_ttx));
-        }
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (mode == PV_VOTE_DENSE)
-        k_vote_bytes<PV_VOTE_DENSE, 4><<<grid, 256, 0, s>>>(ba);
-    else
-        k_vote_bytes<PV_VOTE_OR, 4><<<grid, 256, 0, s>>>(ba);
-    return last();
-}
-
-int pv_generate_hypothesis_vp(const float *direct, const float *coords, const int32_t *idxs, float *hypo,
-                              int32_t tn, int32_t vn, int32_t hn, pv_stream_t stream) {
-    if (!direct || !coords || !idxs || !hypo || tn <= 0 || vn <= 0 || hn < 0) return PV_EINVAL;
-    if (hn == 0) return PV_OK;
-    int64_t n = (int64_t)hn * vn;
-    k_generate_vp<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(direct, coords, idxs, hypo, tn, vn,
-                                                                                 hn);
-    return last();
-}
-
-int pv_voting_for_hypothesis_vp(const float *direct, const float *coords, const float *hypo, uint8_t *inliers,
-                                int32_t tn, int32_t vn, int32_t hn, float inlier_thresh, pv_stream_t stream) {
-    if (!direct || !coords || !hypo || !inliers || tn < 0 || vn <= 0 || hn < 0) return PV_EINVAL;
-    int64_t n = (int64_t)hn * vn * tn;
-    if (n == 0) return PV_OK;
-    k_vote_vp<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(direct, coords, hypo, inliers, tn, vn, hn,
-                                                                            inlier_thresh);
-    return last();
-}
+extern "C" {
 
 int pv_vote_counts(const float *direct, const float *coords, const float *hypo, int32_t *counts, int32_t tn,
                    int32_t vn, int32_t hn, float inlier_thresh, pv_stream_t stream) {
@@ -2511,31 +1458,6 @@ int pv_vote_counts(const float *direct, const float *coords, const float *hypo, 
     return last();
 }
 
-// debug only (not in pvvote.h): wave min / max of 64 floats per wave -> out[2 * wave + {0, 1}]
-// debug only (not in pvvote.h): ntiles products A[i] (32 x 8 fp16) x B[i] (8 x 32 fp16) -> D[i]
-// (32 x 32 f32) on v_mfma_f32_32x32x8_f16 with a zero accumulator (the vote kernel's sums)
-int pv_debug_mfma_sums(const uint16_t *A, const uint16_t *B, float *D, int32_t ntiles, pv_stream_t stream) {
-    if (!A || !B || !D || ntiles <= 0) return PV_EINVAL;
-    k_debug_mfma_sums<<<(unsigned)ntiles, 64, 0, (hipStream_t)stream>>>(A, B, D);
-    return last();
-}
-
-int pv_debug_wave_minmax(const float *in, float *out, int32_t nwaves, pv_stream_t stream) {
-    if (!in || !out || nwaves <= 0) return PV_EINVAL;
-    k_debug_minmax<<<(unsigned)nwaves, 64, 0, (hipStream_t)stream>>>(in, out);
-    return last();
-}
-
-
-#ifdef PVV_PROFILE
-// profiling builds only (never during a capture): work left out of the next
-// launches (g_abl's bits); outputs are wrong
-int pv_debug_set_ablation(int32_t m) {
-    g_abl = m;
-    return PV_OK;
-}
-#endif
-
 #ifdef PVV_TRACE
 // trace builds only: per-wave timestamps of the next pipeline vote launches
 void pv_debug_set_vote_trace(uint64_t *buf) { g_vote_trace = buf; }
@@ -2544,142 +1466,6 @@ void pv_debug_set_vote_trace(uint64_t *buf) { g_vote_trace = buf; }
 // (0 matrix-core k_vote_mfma, 1 VALU k_vote_count); returns the previous
 int pv_debug_set_vote_kernel(int32_t which) {
     return g_vote_kernel.exchange(which == 1 ? 1 : 0, std::memory_order_relaxed);
-}
-// test hook (not in pvvote.h): the byte kernel's band-queue mode (4: one-entry
-// queue, so band rows take the in-kernel exact pass); returns the previous
-int pv_debug_set_bytes_mode(int32_t dbg) {
-    return g_bytes_dbg.exchange(dbg == 4 ? 4 : 0, std::memory_order_relaxed);
-}
-#ifdef PVVOTE_TRACE_U1
-int pv_debug_set_bytes_trace(uint64_t *buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_btrace), &buf, sizeof(buf)); }
-#endif
-
-size_t pv_v3_workspace_size(int32_t b, int32_t H, int32_t W, int32_t vn, int32_t n_hyp) {
-    if (b <= 0 || H <= 0 || W <= 0 || vn <= 0 || n_hyp <= 0) return 0;
-    return carve(nullptr, b, H, W, vn, n_hyp).total;
-}
-
-int pv_v3_kernel_launches(int32_t b, int32_t H, int32_t W, int32_t vn, int32_t n_hyp) {
-    if (b <= 0 || H <= 0 || W <= 0 || vn <= 0 || n_hyp <= 0) return 0;
-    const int64_t P = (int64_t)H * W;
-    const int nblk = (int)((P + kCompactChunk - 1) / kCompactChunk);
-    const int64_t per_img = vote_units_per_image(vn, n_hyp, P);
-    if (!per_img) return 0;
-    const int chunk = images_per_vote_launch(b, per_img);
-    const bool pre = hyp_pregen_used(n_hyp);
-    return 2 + (pre && !hyp_fused(n_hyp, nblk) ? 1 : 0) + (b + chunk - 1) / chunk + 1;
-}
-
-int pv_ransac_voting_v3(const pv_image_desc *img, const pv_vote_params *prm, float *out, void *workspace,
-                        size_t workspace_bytes, const pv_v3_diag *diag, pv_stream_t stream) {
-    int r = check_desc(img);
-    if (r) return r;
-    if (!prm || !out || prm->round_hyp_num <= 0) return PV_EINVAL;
-    const int nh = prm->round_hyp_num;
-    Workspace w = carve(workspace, pipeline_images(img), img->H, img->W, img->vn, nh);
-    if (!workspace || workspace_bytes < w.total) return PV_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    pv_v3_diag dg{};
-    if (diag) dg = *diag;
-    if ((r = front_half(img, prm, nh, false, w, dg, s))) return r;
-    const int b = pipeline_images(img), vn = img->vn;
-    const int64_t P = (int64_t)img->H * img->W;
-    if (!(g_abl & 8)) launch_refine(w, hyp_pregen_used(nh), b, vn, nh, P, prm, out, dg, s);
-    if ((r = last())) return r;
-    if (dg.counts) {
-        hipError_t e = hipMemcpyAsync(dg.counts, w.counts, sizeof(int32_t) * (size_t)b * vn * nh,
-                                      hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) return rc(e);
-    }
-    return PV_OK;
-}
-
-int pv_ransac_voting_v5(const pv_image_desc *img, const pv_vote_params *prm, float conf_thresh, float *out,
-                        float *conf, void *workspace, size_t workspace_bytes, const pv_v3_diag *diag,
-                        pv_stream_t stream) {
-    if (!conf) return PV_EINVAL;
-    int r = pv_ransac_voting_v3(img, prm, out, workspace, workspace_bytes, diag, stream);
-    if (r) return r;
-    Workspace w = carve(workspace, pipeline_images(img), img->H, img->W, img->vn, prm->round_hyp_num);
-    const int64_t P = (int64_t)img->H * img->W;
-    launch_point_conf(w, out, pipeline_images(img), img->vn, P, conf_thresh, conf, (hipStream_t)stream);
-    return last();
-}
-
-int pv_ransac_motion_voting(const pv_image_desc *img, float *out, pv_stream_t stream) {
-    int r = check_desc(img);
-    if (r) return r;
-    if (!out || img->mask_kind == PV_MASK_SEG_F32 || img->mask_kind == PV_MASK_SEG_F16) return PV_EINVAL;
-    if (img->ncls > 0) return PV_EINVAL;   // one object per image only
-    hipStream_t s = (hipStream_t)stream;
-    const int b = img->b, vn = img->vn;
-    // stream-ordered, zeroed scratch: sums [b][vn][2] f64, counts [b], tickets [b]
-    const size_t acc_bytes = sizeof(double) * 2 * (size_t)b * vn, bytes = acc_bytes + sizeof(int32_t) * 2 * b;
-    char *scr = nullptr;
-    hipError_t e = hipMallocAsync((void **)&scr, bytes, s);
-    if (e != hipSuccess) return rc(e);
-    e = hipMemsetAsync(scr, 0, bytes, s);
-    if (e != hipSuccess) return rc(e);
-    MaskView m;
-    VertexView vx;
-    image_views(img, &m, &vx);
-    int32_t *cnt = (int32_t *)(scr + acc_bytes);
-    r = launch_motion(img->mask_kind, m, vx, b, img->H, img->W, vn, (double *)scr, cnt, cnt + b, out, s);
-    if (r) return r;
-    r = last();
-    e = hipFreeAsync(scr, s);
-    return r ? r : rc(e);
-}
-
-static int evd_front(const pv_image_desc *img, const pv_vote_params *prm, void *workspace, size_t workspace_bytes,
-                     Workspace *w, int *nh, hipStream_t s, const pv_v3_diag *diag = nullptr) {
-    int r = check_desc(img);
-    if (r) return r;
-    if (!prm || prm->round_hyp_num <= 0 || prm->min_hyp_num <= 0) return PV_EINVAL;
-    int rounds = (prm->min_hyp_num + prm->round_hyp_num - 1) / prm->round_hyp_num;
-    *nh = rounds * prm->round_hyp_num;
-    *w = carve(workspace, pipeline_images(img), img->H, img->W, img->vn, *nh);
-    if (!workspace || workspace_bytes < w->total) return PV_EWORKSPACE;
-    pv_v3_diag ev{};     // the diag's timing events only (bench.py's U4 line)
-    if (diag) {
-        ev.ev_vote_begin = diag->ev_vote_begin;
-        ev.ev_vote_end = diag->ev_vote_end;
-        ev.ev_compact_end = diag->ev_compact_end;
-    }
-    return front_half(img, prm, *nh, true, *w, ev, s);
-}
-
-int pv_estimate_voting_distribution_with_mean_diag(const pv_image_desc *img, const pv_vote_params *prm,
-                                                   const float *mean, float *cov, void *workspace,
-                                                   size_t workspace_bytes, const pv_v3_diag *diag,
-                                                   pv_stream_t stream) {
-    if (!mean || !cov) return PV_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    Workspace w;
-    int nh = 0;
-    int r = evd_front(img, prm, workspace, workspace_bytes, &w, &nh, s, diag);
-    if (r) return r;
-    launch_evd_with_mean(w, pipeline_images(img), img->vn, nh, prm->min_num, prm->min_hyp_num, mean, cov, s);
-    return last();
-}
-
-int pv_estimate_voting_distribution_with_mean(const pv_image_desc *img, const pv_vote_params *prm,
-                                              const float *mean, float *cov, void *workspace,
-                                              size_t workspace_bytes, pv_stream_t stream) {
-    return pv_estimate_voting_distribution_with_mean_diag(img, prm, mean, cov, workspace, workspace_bytes, nullptr,
-                                                          stream);
-}
-
-int pv_estimate_voting_distribution(const pv_image_desc *img, const pv_vote_params *prm, float *mean, float *cov,
-                                    void *workspace, size_t workspace_bytes, pv_stream_t stream) {
-    if (!mean || !cov || !prm || prm->topk <= 0) return PV_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    Workspace w;
-    int nh = 0;
-    int r = evd_front(img, prm, workspace, workspace_bytes, &w, &nh, s);
-    if (r) return r;
-    launch_evd_topk(w, pipeline_images(img), img->vn, nh, prm->min_num, prm->topk, mean, cov, s);
-    return last();
 }
 
 }  // extern "C"

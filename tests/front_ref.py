@@ -1,5 +1,5 @@
 """The voting front half's counter RNG (pvnet_amd/csrc/pv_rng.h) and what front_half
-(pvvote.hip) makes of a call's seed, restated in numpy: uint64 / uint32 arithmetic that
+(pvpipeline.hip) makes of a call's seed, restated in numpy: uint64 / uint32 arithmetic that
 wraps, one float32 step.  tests/test_front_ref.py requires the four functions to equal
 pv_rng.h compiled for the host bit for bit; tests/test_gpu_front_half.py then injects
 ``pairs`` and ``keep_mask`` into a call and requires what the seeded call gives.

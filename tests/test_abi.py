@@ -64,8 +64,10 @@ def test_default_build_exports_test_hooks_only(default_cdll):
 
 
 # What libpvvote.so exported (nm -D --defined-only) while the vote library was one
-# translation unit; the launchers between its translation units (namespace pvv)
-# are hidden, so the list holds still.
+# translation unit.  Its entries now come from pvvote.hip (the fused vote/count's own),
+# pvapi.hip (the stand-alone API kernels'), pvpipeline.hip (the pipeline and the general
+# ABI) and the stage files; the launchers between them (namespace pvv, pv_stages.h) are
+# hidden, so the list holds still.
 PV_EXPORTS = """
 pv_build_config pv_conv3x3_ex_f16 pv_conv3x3_f16 pv_conv3x3_workspace_bytes pv_conv3x3_workspace_counter_bytes
 pv_conv64_f16 pv_conv_epilogue_f16 pv_conv_epilogue_f32 pv_debug_lookback_self pv_debug_mfma_sums

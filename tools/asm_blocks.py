@@ -1,6 +1,8 @@
 """Debug: per-basic-block instruction counts of one kernel in the device
 assembly of the translation unit that holds it.
-usage: asm_blocks.py NAME-SUBSTRING [TU.hip (default pvvote.hip: the vote kernels) | FILE.s]
+usage: asm_blocks.py NAME-SUBSTRING [TU.hip | FILE.s]
+TU.hip defaults to pvvote.hip, the fused vote/count kernels alone (k_vote_mfma,
+k_vote_count, k_hyp_gen); k_vote_bytes and the other API kernels are pvapi.hip's.
 A TU is read from csrc/TU.gfx950.s, which pvnet_amd.build.asm(TU) writes; it is
 compiled again only if that file is older than the sources."""
 import os

@@ -1,10 +1,9 @@
 """Randomised parity sweep of the API vote kernels against the C oracle:
-voting_for_hypothesis (dense with both byte kernels, and OR) and vote_counts
+voting_for_hypothesis (dense and OR: the one byte kernel) and vote_counts
 (k_vote_mfma when hn is a multiple of 512's groups, else k_vote_count) over
 random tn / vn / hn / thresholds / coordinate spans / degenerate pixels and
 hypotheses.  GPU only; prints one line per case and a summary, exits 1 on the
 first mismatch (the case's parameters are printed)."""
-import ctypes
 import sys
 import time
 
@@ -13,12 +12,8 @@ import torch
 
 sys.path.insert(0, ".")
 from oracle import oracle as O  # noqa: E402
-from pvnet_amd import _lib  # noqa: E402
 from pvnet_amd import ransac_voting as rv  # noqa: E402
 
-L = _lib.load()
-L.pv_debug_set_bytes_mfma.argtypes = [ctypes.c_int32]
-L.pv_debug_set_bytes_mfma.restype = ctypes.c_int32
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 dev = torch.device("cuda:0")
 t_end = time.time() + budget
@@ -50,12 +45,10 @@ while time.time() < t_end:
     ref = np.zeros((hn, vn, tn), np.uint8)
     O.voting_for_hypothesis(direct, coords, hyp, ref, thr)
     dd, cc, hh = (torch.from_numpy(a).to(dev) for a in (direct, coords, hyp))
-    for name, mfma, dense in (("valu-dense", 0, True), ("mfma-dense", 1, True), ("or", 0, False)):
-        prev = L.pv_debug_set_bytes_mfma(mfma)
+    for name, dense in (("dense", True), ("or", False)):
         init = np.zeros_like(ref) if dense else (rng.random(ref.shape) < 0.1).astype(np.uint8) * 5
         out = torch.from_numpy(init.copy()).to(dev)
         (rv.voting_for_hypothesis_dense if dense else rv.voting_for_hypothesis)(dd, cc, hh, out, thr)
-        L.pv_debug_set_bytes_mfma(prev)
         exp = ref if dense else np.where(ref == 1, 1, init).astype(np.uint8)
         got = out.cpu().numpy()
         if not np.array_equal(got, exp):
