@@ -25,6 +25,7 @@
 #include "../../include/pvvote.h"
 #include "pv_tunables.h"
 #include "pv_rng.h"
+#include "pv_hypclass.h"
 
 namespace pvv __attribute__((visibility("hidden"))) {
 
@@ -37,9 +38,8 @@ constexpr int kRT = PVV_REFINE_T;            // refine block threads
 // (ratio, index), each value as one 16-B pair of tagged 8-B granules
 constexpr int kRefineGran = 6;
 constexpr int kRefineLdsHyp = 1024;          // hypotheses per keypoint kept in LDS (more: k_refine_solve<true>)
-// domain of the fast test's error bound
-constexpr float kHypMax = 1.0e17f;           // |hx|,|hy| above -> exact-only hypothesis
-constexpr float kLattice = 2.5e-6f;          // |h - round(h)| below (both axes) -> exact-only
+// domain of the fast test's error bound (the hypotheses' side, kHypMax / kLattice / kMHypMax, hyp_exact_only
+// and hyp_class: pv_hypclass.h, included above)
 constexpr float kN1Max = 1.0e18f;            // |direction| above -> exact-only pixel
 // The two norm1 tests of a pixel on its squared norm s (fl(fl(nx nx) + fl(ny ny)),
 // the reference's own sum): the correctly rounded sqrtf is monotone, so
@@ -114,15 +114,6 @@ __device__ __forceinline__ bool exact_intersect(float dx0, float dy0, float cx0,
     *oy = (nx1 * p0 - nx0 * p1) / d0;
     *ox = (ny1 * p0 - ny0 * p1) / d1;
     return true;
-}
-
-// Is hypothesis (hx, hy) outside the fast test's domain?  Non-finite, huge, or
-// within 2.5e-6 of an integer lattice point (pixel centres are integers, so
-// only such hypotheses can come within the reference's norm2 < 1e-6 guard).
-__device__ __forceinline__ bool hyp_exact_only(float hx, float hy) {
-    bool big = !(fabsf(hx) <= kHypMax) || !(fabsf(hy) <= kHypMax);   // also NaN/inf
-    bool lat = fabsf(hx - rintf(hx)) < kLattice && fabsf(hy - rintf(hy)) < kLattice;
-    return big || lat;
 }
 
 __device__ __forceinline__ uint64_t ballot(bool x) { return __ballot(x); }
@@ -214,11 +205,15 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t image_rsrc(const VertexView &v
 // workspace
 // --------------------------------------------------------------------------
 struct Workspace {
+    // the hypotheses' classes (pv_hypclass.h), the workspace's first bytes: per 32 hypotheses of a keypoint the
+    // ballot of the fast ones and the ballot of the exact-only ones, OR-ed in by the producers (compact_hyp,
+    // k_hyp_gen) and read by the pipeline's k_vote_mfma; nset = 4 * ceil(nh / 128), bits past nh stay 0
+    uint32_t *hypcls;   // [b][vn][nset][2] zeroed by k_fg_count
     int32_t *counts;    // [b][vn][nh]   zeroed by k_fg_count
     uint4 *refslot;     // [b][vn][kRefineNJ][kRefineGran] zeroed by k_fg_count: k_refine_solve's tagged partials
     int32_t *dsagg;     // [b][nblk]     zeroed by k_fg_count: downsampled count + 1 per block (look-back)
     int32_t *confc;     // [b][vn][2]    zeroed by k_fg_count: v5 confidence count, ticket
-    int64_t zero_words; // counts + refslot + dsagg + confc (contiguous)
+    int64_t zero_words; // hypcls + counts + refslot + dsagg + confc (contiguous, from hypcls)
     int32_t *tn;        // [b] compacted pixels (0 = image skipped)
     int32_t *fgtot;     // [b] foreground before downsampling
     int32_t *blkcnt;    // [b][nblk]
@@ -231,6 +226,9 @@ struct Workspace {
     size_t total;
 };
 
+// 32-hypothesis sets per keypoint in Workspace::hypcls: four per 128-hypothesis group of the vote's work index
+__host__ __device__ inline int64_t hyp_sets(int nh) { return 4 * (((int64_t)nh + 2 * kWave - 1) / (2 * kWave)); }
+
 inline Workspace carve(void *base, int b, int H, int W, int vn, int nh) {
     Workspace w{};
     int64_t P = (int64_t)H * W;
@@ -240,8 +238,10 @@ inline Workspace carve(void *base, int b, int H, int W, int vn, int nh) {
     auto take = [&](int64_t bytes) { char *q = p ? p + off : nullptr; off = align_up(off + bytes, 256); return q; };
     const int64_t ncnt = align_up((int64_t)b * vn * nh, 4);            // refslot 16-B aligned
     const int64_t nslot = (int64_t)b * vn * kRefineNJ * kRefineGran;
-    w.zero_words = ncnt + 4 * nslot + b * nblk + 2 * (int64_t)b * vn;
-    w.counts = (int32_t *)take(4 * w.zero_words);
+    const int64_t ncls = align_up(2 * (int64_t)b * vn * hyp_sets(nh), 4);
+    w.zero_words = ncls + ncnt + 4 * nslot + b * nblk + 2 * (int64_t)b * vn;
+    w.hypcls = (uint32_t *)take(4 * w.zero_words);
+    w.counts = w.hypcls ? (int32_t *)(w.hypcls + ncls) : nullptr;
     w.refslot = w.counts ? (uint4 *)(w.counts + ncnt) : nullptr;
     w.dsagg = w.counts ? (int32_t *)(w.refslot + nslot) : nullptr;
     w.confc = w.counts ? w.dsagg + b * nblk : nullptr;

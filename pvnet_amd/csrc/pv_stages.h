@@ -32,6 +32,7 @@ struct HypGen {
     const uint8_t *keep;
     float2 *hyp_out;            // [b][nh][vn]
     float2 *hypv_out;           // [b][vn][nh]
+    uint32_t *hypcls;           // [b][vn][nset][2] the classes' ballots (Workspace::hypcls, zeroed by k_fg_count)
     float *diag_hyp;            // [b][nh][vn][2] or nullptr
     uint64_t *keptbits;         // downsampled images: the compaction blocks' kept ballots [b][nblk][4]
 };
@@ -56,6 +57,38 @@ int compact(const CompactArgs &a);
 // ---- hypotheses and the fused vote/count (pvvote.hip) ---------------------
 constexpr int kHypLane = 2;                 // hypotheses per lane of a vote wave
 constexpr int kGroup = kWave * kHypLane;    // hypotheses per wave: a hypothesis group, the unit of the vote's work index
+static_assert(kGroup == 128, "hyp_sets (pv_common.h): four 32-hypothesis sets per group");
+
+// The classes of a producer block's hypotheses into the classes' ballots (Workspace::hypcls, zeroed before).
+// Every thread of the 256 calls it; an active one holds item r = h * vn + v of image b (consecutive threads
+// hold consecutive items) and cls = hyp_class of the value it stored.  A block's items of one keypoint fall
+// into a few 32-hypothesis sets, each shared with the neighbouring blocks: the bits are gathered in LDS at the
+// slot of the set's first thread in the block (its leader), which ORs the two words into memory -- two or
+// three atomics per word over the grid, not one per hypothesis on the same address.  lds: 512 words.
+__device__ __forceinline__ void hypcls_block_put(uint32_t *hypcls, uint32_t *lds, int b, int vn, int nh, int r,
+                                                 bool active, uint32_t cls) {
+    const int t = (int)threadIdx.x;
+    lds[t] = 0;
+    lds[256 + t] = 0;
+    __syncthreads();
+    int lead = t, h = 0, v = 0;
+    if (active) {
+        h = r / vn;
+        v = r - h * vn;
+        const int r0 = max(r - t, 0);                       // the block's first item of this image
+        const int hf = (r0 - v + vn - 1) / vn;              // keypoint v's first hypothesis in the block
+        lead = t - (h - max(h & ~31, hf)) * vn;             // the thread of (that or the set's first one, v)
+        if (cls & kHypFast) atomicOr(&lds[lead], 1u << (h & 31));
+        if (cls & kHypExact) atomicOr(&lds[256 + lead], 1u << (h & 31));
+    }
+    __syncthreads();
+    if (active && lead == t) {
+        uint32_t *w = hypcls + (((int64_t)b * vn + v) * hyp_sets(nh) + (h >> 5)) * 2;
+        const uint32_t f = lds[t], x = lds[256 + t];
+        if (f) atomicOr(w, f);
+        if (x) atomicOr(w + 1, x);
+    }
+}
 
 struct VoteArgs {
     const float4 *pex;          // PREPPED: exact data (cx, cy, nx, ny), same layout
@@ -64,6 +97,7 @@ struct VoteArgs {
     const float2 *hyp;          // !GEN: hyp[b*hyp_sb + v*hyp_sv + h*hyp_sh]
     float2 *hyp_out;            // GEN: generated hypotheses [b][nh][vn]
     float2 *hypv_out;           // k_hyp_gen: keypoint-major copy [b][vn][nh]
+    uint32_t *hypcls;           // k_hyp_gen writes, the pipeline's k_vote_mfma reads: Workspace::hypcls [b][vn][nset][2]
     int64_t hyp_sb, hyp_sv, hyp_sh;
     float *diag_hyp;            // GEN: optional copy [b][nh][vn][2]
     const int32_t *idxs;        // GEN: pixel pairs [b][nh][vn][2], or nullptr (counter RNG)
@@ -75,8 +109,7 @@ struct VoteArgs {
     int32_t b0;                 // GEN: batch index of image 0 of this launch (RNG key: the same pairs in any chunking)
     float thr, tau, gzf, gzr;
     uint64_t *trace;            // debug: per-wave (start, end) s_memrealtime stamps, or nullptr
-    int32_t rw[4];              // SH, four resident rounds of blocks: work weights per round (0: even)
-    BandConsts bk;              // k_vote_mfma: the band re-check's constants (pv_band.h), made by launch_vote
+    int32_t rw[4];              // k_vote_count, four resident rounds of blocks: work weights per round (0: even)
 };
 
 // thr, tau, gzf, gzr and fast of `va` from the inlier threshold (the byte kernel takes its own from a scratch VoteArgs)
@@ -86,7 +119,8 @@ bool hyp_pregen_used(int nh);
 // k_hyp_gen over va's b images: hyp_out and hypv_out
 void launch_hyp_gen(const VoteArgs &va, hipStream_t s);
 // the fused vote/count of one launch chunk on compacted pixels (va.pex): k_vote_mfma, or k_vote_count
-void launch_pipeline_vote(const VoteArgs &va, int64_t pixel_steps, hipStream_t s);
+// (PV_EINVAL, nothing launched: k_vote_mfma's turn without pre-generated hypotheses and their classes)
+int launch_pipeline_vote(const VoteArgs &va, int64_t pixel_steps, hipStream_t s);
 
 // ---- refine and v5 confidence (pvrefine.hip) ------------------------------
 // k_refine_solve over the workspace's counts; hypv: the hypotheses keypoint-major (w.hypv)

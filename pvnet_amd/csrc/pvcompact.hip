@@ -523,78 +523,85 @@ __device__ void compact_hyp(const VertexView &vx, int H, int W, int nblk, const 
     }
     n = min(n, (int)P);
     if (n <= 0) return;
-    // ---- this thread's hypothesis: item i = (h, v) of image b
+    // ---- this thread's hypothesis: item i = (h, v) of image b; returns its class (hyp_class)
     const int i = hb * 256 + (int)threadIdx.x;
-    if (i >= g.nh * g.vn) return;
-    const int h = i / g.vn, v = i - h * g.vn;
-    const int64_t gid = ((int64_t)b * g.nh + h) * g.vn + v;
-    int t[2];
-    if (g.idxs) {
-        t[0] = min(max(g.idxs[gid * 2], 0), n - 1);
-        t[1] = min(max(g.idxs[gid * 2 + 1], 0), n - 1);
-    } else {
-        const uint64_t key = (uint64_t)gid;
-        t[0] = rand_index(g.seed, key * 2, n);
-        t[1] = rand_index(g.seed, key * 2 + 1, n);
-    }
-    int jj[2], rr[2];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {                  // the last chunk with pre <= t (never an empty one)
-        int lo = 0, hi = nblk - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (pre[mid] <= t[e]) lo = mid; else hi = mid - 1;
+    const bool act = i < g.nh * g.vn;
+    auto make = [&]() -> uint32_t {
+        const int h = i / g.vn, v = i - h * g.vn;
+        const int64_t gid = ((int64_t)b * g.nh + h) * g.vn + v;
+        int t[2];
+        if (g.idxs) {
+            t[0] = min(max(g.idxs[gid * 2], 0), n - 1);
+            t[1] = min(max(g.idxs[gid * 2 + 1], 0), n - 1);
+        } else {
+            const uint64_t key = (uint64_t)gid;
+            t[0] = rand_index(g.seed, key * 2, n);
+            t[1] = rand_index(g.seed, key * 2 + 1, n);
         }
-        jj[e] = lo;
-        rr[e] = t[e] - pre[lo];
-    }
-    uint64_t w0[4], w1[4];
+        int jj[2], rr[2];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        w0[q] = fgbits[((int64_t)b * nblk + jj[0]) * 4 + q];
-        w1[q] = fgbits[((int64_t)b * nblk + jj[1]) * 4 + q];
-    }
-    if (ds) {                                      // keep only the kept pixels' bits
-        const int32_t *pub = pre + nblk + 1;
-        const bool p0 = g.keptbits && ((pub[jj[0] >> 5] >> (jj[0] & 31)) & 1);
-        const bool p1 = g.keptbits && ((pub[jj[1] >> 5] >> (jj[1] & 31)) & 1);
-        // published: the compaction block's own kept ballots (one load)
+        for (int e = 0; e < 2; ++e) {                  // the last chunk with pre <= t (never an empty one)
+            int lo = 0, hi = nblk - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (pre[mid] <= t[e]) lo = mid; else hi = mid - 1;
+            }
+            jj[e] = lo;
+            rr[e] = t[e] - pre[lo];
+        }
+        uint64_t w0[4], w1[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            if (p0) w0[q] = ld_agent(&g.keptbits[((int64_t)b * nblk + jj[0]) * 4 + q]);
-            if (p1) w1[q] = ld_agent(&g.keptbits[((int64_t)b * nblk + jj[1]) * 4 + q]);
+            w0[q] = fgbits[((int64_t)b * nblk + jj[0]) * 4 + q];
+            w1[q] = fgbits[((int64_t)b * nblk + jj[1]) * 4 + q];
         }
+        if (ds) {                                      // keep only the kept pixels' bits
+            const int32_t *pub = pre + nblk + 1;
+            const bool p0 = g.keptbits && ((pub[jj[0] >> 5] >> (jj[0] & 31)) & 1);
+            const bool p1 = g.keptbits && ((pub[jj[1] >> 5] >> (jj[1] & 31)) & 1);
+            // published: the compaction block's own kept ballots (one load)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (p0 && p1) break;
-            uint64_t m0 = w0[q], m1 = w1[q], x0 = p0 ? 0 : w0[q], x1 = p1 ? 0 : w1[q];
-            if (!p0) m0 = 0;
-            if (!p1) m1 = 0;
-            while (x0) { const int z = __builtin_ctzll(x0); x0 &= x0 - 1;
-                         if (kept((int64_t)jj[0] * kCompactChunk + q * 64 + z)) m0 |= 1ull << z; }
-            while (x1) { const int z = __builtin_ctzll(x1); x1 &= x1 - 1;
-                         if (kept((int64_t)jj[1] * kCompactChunk + q * 64 + z)) m1 |= 1ull << z; }
-            w0[q] = m0; w1[q] = m1;
+            for (int q = 0; q < 4; ++q) {
+                if (p0) w0[q] = ld_agent(&g.keptbits[((int64_t)b * nblk + jj[0]) * 4 + q]);
+                if (p1) w1[q] = ld_agent(&g.keptbits[((int64_t)b * nblk + jj[1]) * 4 + q]);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (p0 && p1) break;
+                uint64_t m0 = w0[q], m1 = w1[q], x0 = p0 ? 0 : w0[q], x1 = p1 ? 0 : w1[q];
+                if (!p0) m0 = 0;
+                if (!p1) m1 = 0;
+                while (x0) { const int z = __builtin_ctzll(x0); x0 &= x0 - 1;
+                             if (kept((int64_t)jj[0] * kCompactChunk + q * 64 + z)) m0 |= 1ull << z; }
+                while (x1) { const int z = __builtin_ctzll(x1); x1 &= x1 - 1;
+                             if (kept((int64_t)jj[1] * kCompactChunk + q * 64 + z)) m1 |= 1ull << z; }
+                w0[q] = m0; w1[q] = m1;
+            }
         }
-    }
-    constexpr int ES = VK == PV_VERTEX_F32 ? 4 : 2;
-    const __amdgpu_buffer_rsrc_t vr = image_rsrc<MC>(vx, b, ES);
-    const int s4 = (int)(vx.s[4] * ES);
-    float cx[2], cy[2], nx[2], ny[2];
+        constexpr int ES = VK == PV_VERTEX_F32 ? 4 : 2;
+        const __amdgpu_buffer_rsrc_t vr = image_rsrc<MC>(vx, b, ES);
+        const int s4 = (int)(vx.s[4] * ES);
+        float cx[2], cy[2], nx[2], ny[2];
 #pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        const int q = select_bit(e == 0 ? w0 : w1, rr[e]);
-        const uint32_t p = (uint32_t)jj[e] * kCompactChunk + (uint32_t)q;
-        const int r = (int)(p / (uint32_t)W), col = (int)(p - (uint32_t)r * W);
-        cx[e] = (float)col;
-        cy[e] = (float)r;
-        read_dir<VK>(vr, (int)((r * vx.s[1] + col * vx.s[2] + v * vx.s[3]) * ES), s4, nx[e], ny[e]);
-    }
-    float x = 0.f, y = 0.f, ox, oy;
-    if (exact_intersect(nx[0], ny[0], cx[0], cy[0], nx[1], ny[1], cx[1], cy[1], &ox, &oy)) { x = ox; y = oy; }
-    g.hyp_out[gid] = make_float2(x, y);
-    if (g.diag_hyp) { g.diag_hyp[gid * 2] = x; g.diag_hyp[gid * 2 + 1] = y; }
-    g.hypv_out[((int64_t)b * g.vn + v) * g.nh + h] = make_float2(x, y);
+        for (int e = 0; e < 2; ++e) {
+            const int q = select_bit(e == 0 ? w0 : w1, rr[e]);
+            const uint32_t p = (uint32_t)jj[e] * kCompactChunk + (uint32_t)q;
+            const int r = (int)(p / (uint32_t)W), col = (int)(p - (uint32_t)r * W);
+            cx[e] = (float)col;
+            cy[e] = (float)r;
+            read_dir<VK>(vr, (int)((r * vx.s[1] + col * vx.s[2] + v * vx.s[3]) * ES), s4, nx[e], ny[e]);
+        }
+        float x = 0.f, y = 0.f, ox, oy;
+        if (exact_intersect(nx[0], ny[0], cx[0], cy[0], nx[1], ny[1], cx[1], cy[1], &ox, &oy)) { x = ox; y = oy; }
+        g.hyp_out[gid] = make_float2(x, y);
+        if (g.diag_hyp) { g.diag_hyp[gid * 2] = x; g.diag_hyp[gid * 2 + 1] = y; }
+        g.hypv_out[((int64_t)b * g.vn + v) * g.nh + h] = make_float2(x, y);
+        return hyp_class(x, y);
+    };
+    const uint32_t cls = act ? make() : 0u;
+    // the classes' ballots, gathered per block in LDS (pre[] is free once every thread has its pixels)
+    __syncthreads();
+    hypcls_block_put(g.hypcls, (uint32_t *)pre, b, g.vn, g.nh, i, act, cls);
 }
 
 // TASKS (grids above kFgWideAbove blocks, i.e. batches): the records are
@@ -635,10 +642,10 @@ struct CompactStage {
         if (g_abl & 16) {
         } else if (wide)
             k_fg_count<KIND, EVD, kFgWideCPB><<<dim3((a->nblk + kFgWideCPB - 1) / kFgWideCPB, a->b), 256, 0, a->s>>>(
-                a->m, a->H, a->W, a->ws.blkcnt, a->ws.fgbits, a->ws.grpcnt, a->nblk, a->ws.counts, a->ws.zero_words);
+                a->m, a->H, a->W, a->ws.blkcnt, a->ws.fgbits, a->ws.grpcnt, a->nblk, (int32_t *)a->ws.hypcls, a->ws.zero_words);
         else
             k_fg_count<KIND, EVD, 1><<<dim3(a->nblk, a->b), 256, 0, a->s>>>(a->m, a->H, a->W, a->ws.blkcnt, a->ws.fgbits,
-                                                                          nullptr, a->nblk, a->ws.counts,
+                                                                          nullptr, a->nblk, (int32_t *)a->ws.hypcls,
                                                                           a->ws.zero_words);
         if (g_abl & 1) return last();
         const bool f32 = a->vx.kind == PV_VERTEX_F32;
@@ -658,11 +665,11 @@ int compact_multi(const CompactArgs *a) {
     const bool wide = (int64_t)a->nblk * a->b > kFgWideAbove;   // the same for both kernels
     if (wide)
         k_label_count<KIND, kFgWideCPB><<<dim3((a->nblk + kFgWideCPB - 1) / kFgWideCPB, bi), 256, 0, a->s>>>(
-            a->m, a->H, a->W, a->ncls, a->ws.blkcnt, a->ws.fgbits, a->ws.grpcnt, a->nblk, a->ws.counts,
+            a->m, a->H, a->W, a->ncls, a->ws.blkcnt, a->ws.fgbits, a->ws.grpcnt, a->nblk, (int32_t *)a->ws.hypcls,
             a->ws.zero_words);
     else
         k_label_count<KIND, 1><<<dim3(a->nblk, bi), 256, 0, a->s>>>(a->m, a->H, a->W, a->ncls, a->ws.blkcnt,
-                                                                   a->ws.fgbits, nullptr, a->nblk, a->ws.counts,
+                                                                   a->ws.fgbits, nullptr, a->nblk, (int32_t *)a->ws.hypcls,
                                                                    a->ws.zero_words);
     auto launch = [&](auto kernel) {
         kernel<<<dim3(a->nblk + a->hg.nhb, a->b), 256, 0, a->s>>>(

@@ -102,7 +102,7 @@ int front_half(const pv_image_desc *img, const pv_vote_params *prm, int nh, bool
         ca.hg.nh = nh; ca.hg.vn = vn; ca.hg.min_num = prm->min_num; ca.hg.max_num = prm->max_num;
         ca.hg.seed = mix64(prm->seed); ca.hg.kseed = ca.seed;
         ca.hg.idxs = prm->idxs; ca.hg.keep = prm->keep;
-        ca.hg.hyp_out = w.hyp; ca.hg.hypv_out = w.hypv; ca.hg.diag_hyp = dg.hyp;
+        ca.hg.hyp_out = w.hyp; ca.hg.hypv_out = w.hypv; ca.hg.hypcls = w.hypcls; ca.hg.diag_hyp = dg.hyp;
         ca.hg.keptbits = w.keptbits;
     }
     int r = compact(ca);
@@ -120,12 +120,14 @@ int front_half(const pv_image_desc *img, const pv_vote_params *prm, int nh, bool
     va.tn_dev = w.tn; va.tn_host = 0;
     va.b = b; va.vn = vn; va.nh = nh; va.hgn = (nh + kGroup - 1) / kGroup;
     fast_constants(prm->inlier_thresh, &va);
-    // the vote kernel generates the hypotheses itself (item_hyp in its
+    // k_vote_count generates the hypotheses itself (item_hyp in its
     // prologue, overlapped with its first pixel loads) and stores them in
-    // the reference layout; by default (hyp_pregen) one k_hyp_gen launch makes
-    // them first and the vote kernel (k_vote_mfma) reads them keypoint-major
+    // the reference layout; k_vote_mfma (hyp_pregen) reads them keypoint-major
+    // with their classes (w.hypcls), made before it by k_compact's first
+    // blocks or, above kHypMaxChunks, by one k_hyp_gen launch
     if (hyp_pregen_used(nh)) {
         va.hypv_out = w.hypv;
+        va.hypcls = w.hypcls;
         if (!hfuse) launch_hyp_gen(va, s);
         if ((r = last())) return r;
         va.hyp = w.hypv; va.hyp_sb = (int64_t)vn * nh; va.hyp_sv = nh; va.hyp_sh = 1;
@@ -143,11 +145,12 @@ int front_half(const pv_image_desc *img, const pv_vote_params *prm, int nh, bool
         vc.pex += (int64_t)b0 * vn * P;
         vc.hyp_out += (int64_t)b0 * nh * vn;
         if (vc.hyp) vc.hyp += (int64_t)b0 * nh * vn;
+        if (vc.hypcls) vc.hypcls += (int64_t)b0 * vn * hyp_sets(nh) * 2;
         if (vc.diag_hyp) vc.diag_hyp += (int64_t)b0 * nh * vn * 2;
         if (vc.idxs) vc.idxs += (int64_t)b0 * nh * vn * 2;
         vc.counts += (int64_t)b0 * va.cnt_bs;
         vc.tn_dev += b0;
-        if (!(g_abl & 4)) launch_pipeline_vote(vc, nb * per_img, s);
+        if (!(g_abl & 4) && (r = launch_pipeline_vote(vc, nb * per_img, s))) return r;
         if ((r = last())) return r;
     }
     if (dg.ev_vote_end) return rc(hipEventRecord((hipEvent_t)dg.ev_vote_end, s));

@@ -57,10 +57,12 @@ using namespace pvv;
 // K4: hypotheses (KU:11-49) + fused vote/count.
 // counts[b][v][h] += #{t : inlier(h, v, t)}.
 //
-// In the pipeline the vote kernel makes its own hypotheses (pixel pairs from
-// the caller or the counter RNG, RV:553; item_hyp) in its prologue, beside
-// its first pixel loads; the unit whose range starts at pixel 0 of a (b, v,
-// group) stores them in the reference layout (refine stage, diagnostics).
+// k_vote_count (hn not a multiple of 512, or the test hook) makes its own
+// hypotheses in the pipeline (pixel pairs from the caller or the counter RNG,
+// RV:553; item_hyp) in its prologue, beside its first pixel loads; the unit
+// whose range starts at pixel 0 of a (b, v, group) stores them in the
+// reference layout (refine stage, diagnostics).  k_vote_mfma makes none: its
+// hypotheses and their classes come from compact_hyp or k_hyp_gen.
 //
 // k_vote_count: lane = hypothesis (kHypLane = 2 per lane, groups of 128 per
 // wave); the (image, keypoint, group, pixel) space is cut into equal
@@ -107,21 +109,23 @@ __device__ __forceinline__ void round_share(uint32_t total, uint32_t n, uint32_t
 // and index their work from it, so whatever the workspace holds (a caller
 // that hands one workspace to two calls in flight), every pex / hypothesis
 // index stays inside the image's P records
-__device__ __forceinline__ int tn_at(const VoteArgs &a, int b) {
+template <class A>
+__device__ __forceinline__ int tn_at(const A &a, int b) {
     const int n = a.tn_dev ? a.tn_dev[b] : a.tn_host;
     return min(max(n, 0), a.P);
 }
 
 // the reference's operands of pixel t: (cx, cy, nx, ny)
-template <bool PREPPED>
-__device__ __forceinline__ F4 pixel_exact(const VoteArgs &a, int b, int v, int t) {
-    if (PREPPED) {
+template <bool PREPPED, class A>
+__device__ __forceinline__ F4 pixel_exact(const A &a, int b, int v, int t) {
+    if constexpr (PREPPED) {
         const float4 e = a.pex[((int64_t)b * a.vn + v) * a.P + t];
         return F4{e.x, e.y, e.z, e.w};
+    } else {
+        const float2 c = a.coords[(int64_t)b * a.P + t];
+        const float2 d = a.raw[(int64_t)b * a.vn * a.P + (int64_t)v * a.raw_v + (int64_t)t * a.raw_t];
+        return F4{c.x, c.y, d.x, d.y};
     }
-    const float2 c = a.coords[(int64_t)b * a.P + t];
-    const float2 d = a.raw[(int64_t)b * a.vn * a.P + (int64_t)v * a.raw_v + (int64_t)t * a.raw_t];
-    return F4{c.x, c.y, d.x, d.y};
 }
 
 // the hypothesis of lane h (exact value; (0, 0) for a degenerate pair, KU:33-41)
@@ -715,14 +719,22 @@ __global__ void k_abl_empty(int) {}
 // counter RNG, RV:553) and its intersection (KU:11-49), stored in the
 // reference layout and keypoint-major; images without a vote are left alone.
 __global__ __launch_bounds__(256) void k_hyp_gen(VoteArgs a) {
+    __shared__ uint32_t lcls[512];
     const int64_t per = (int64_t)a.nh * a.vn;
     const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= per * a.b) return;
-    const int b = (int)(gid / per);
-    const int r = (int)(gid - b * per);
+    const bool in = gid < per * a.b;
+    const int b = in ? (int)(gid / per) : 0;
+    const int r = in ? (int)(gid - b * per) : 0;
     const int h = r / a.vn, v = r - h * a.vn;
-    const int n = tn_at(a, b);
-    if (n > 0) a.hypv_out[((int64_t)b * a.vn + v) * a.nh + h] = item_hyp<true, true>(a, b, v, h, true, n, true);
+    const bool act = in && tn_at(a, b) > 0;
+    uint32_t cls = 0;
+    if (act) {
+        const float2 hv = item_hyp<true, true>(a, b, v, h, true, tn_at(a, b), true);
+        a.hypv_out[((int64_t)b * a.vn + v) * a.nh + h] = hv;
+        cls = hyp_class(hv.x, hv.y);
+    }
+    // the classes' ballots (every thread: block barriers)
+    hypcls_block_put(a.hypcls, lcls, b, a.vn, a.nh, r, act, cls);
 }
 
 // ==========================================================================
@@ -762,7 +774,7 @@ constexpr int kMSlots = (kMChunk + 255) / 256; // pixels per thread in the block
 constexpr int kMBatch = kMChunk / kMB;         // batches per sub-chunk (24)
 static_assert(kMChunk % kMB == 0 && kMBatch <= 32 && kMChunk <= 512, "hit masks: 2 x 64 bits; queue: 9-bit pixel");
 constexpr int kMSet = 4;                       // 32-hypothesis column sets per wave (128 hypotheses)
-constexpr float kMHypMax = 8.0e6f;             // |hx|, |hy| above -> exact-only (keeps s >= 2^-9)
+// (kMHypMax, |hx|, |hy| from which a hypothesis is exact-only here: pv_hypclass.h, part of hyp_class)
 constexpr float kMRMax = 30000.f;              // sub-chunk radius above -> exact sub-chunk (fp16 range of b)
 constexpr int kMQueue = PVM_QUEUE;             // band pairs queued per wave before a reference pass
 // flagged MFMAs re-checked at a time (2 measured the same as 1).  The re-check
@@ -789,14 +801,51 @@ __device__ __forceinline__ uint4 form_row(float ax, float ay, float b) {
     return make_uint4(pack_h2(axh, axh), pack_h2(axl, ayh), pack_h2(ayh, ayl), pack_h2(bh, bl));
 }
 
+// k_vote_mfma's arguments: only what it reads.  It makes no hypotheses (the
+// pipeline's come from compact_hyp or k_hyp_gen, pv_vote_counts' from the
+// caller), so nothing of the generation (seed, idxs, the reference-layout
+// copies) is here, and each instantiation has its own pixel source.  The
+// layouts are the instantiation's, not arguments: the pipeline's hypotheses and
+// counts are keypoint-major ([b][vn][nh]), pv_vote_counts' are [nh][vn] of one
+// image.
 template <bool PREPPED>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PVM_WPE))) void k_vote_mfma(VoteArgs a) {
+struct MVotePix {               // the pipeline: compacted records and the producers' classes
+    const float4 *pex;          // [b][vn][P] exact data (cx, cy, nx, ny)
+    const uint32_t *hypcls;     // [b][vn][4 hgn][2] ballots of the fast / the exact-only hypotheses (Workspace::hypcls)
+};
+template <>
+struct MVotePix<false> {        // pv_vote_counts: the caller's arrays
+    const float2 *coords;       // coords[t]
+    const float2 *raw;          // raw[v * raw_v + t * raw_t]
+    int32_t raw_v, raw_t;
+};
+template <bool PREPPED>
+struct MVoteArgs : MVotePix<PREPPED> {
+    const float2 *hyp;          // never null (launch_vote)
+    int32_t *counts;
+    const int32_t *tn_dev;      // [b] pixels per image, or nullptr (tn_host)
+    int32_t P, tn_host, b, vn, nh, hgn, fast;
+    float thr, tau, gzf, gzr;
+    float gq, Kb;               // the band re-check's constants (BandConsts, pv_band.h)
+#ifdef PVV_PROFILE
+    int32_t abl;                // the two band ablations' sentinels (7777 / 7778)
+#endif
+#ifdef PVV_TRACE
+    uint64_t *trace;            // per-wave stamps and phase cycles, or nullptr
+#endif
+};
+
+// the 32 columns' bits of a set, for both lane halves (which hold the same columns)
+__device__ __forceinline__ uint64_t both_halves(uint32_t w) { return (uint64_t)w | ((uint64_t)w << 32); }
+
+template <bool PREPPED>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PVM_WPE))) void k_vote_mfma(MVoteArgs<PREPPED> a) {
     const int lane = lane_id();
     const int wid = (int)__builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const int col = lane & 31, half = lane >> 5;
     const int unit = (int)blockIdx.x;
     const uint32_t nunits = gridDim.x;
-    const uint64_t t_start = __builtin_amdgcn_s_memrealtime();
+    [[maybe_unused]] const uint64_t t_start = __builtin_amdgcn_s_memrealtime();
     __builtin_amdgcn_s_setprio(3);
     __shared__ MSlab<PREPPED> slab[2];
     __shared__ QuarterBoxes qb_all[2];
@@ -810,15 +859,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
     uint32_t total = 0;
     for (int b = 0; b < a.b; ++b) total += (uint32_t)(a.vn * ggn) * (uint32_t)tn_at(a, b);
     uint32_t lo, hi;
-    if (a.rw[0] > 0 && nunits % (a.rw[3] > 0 ? 4 : 3) == 0) {
-        round_share(total, nunits, (uint32_t)unit, a.rw, &lo, &hi);
-    } else {
-        even_share(total, nunits, (uint32_t)unit, &lo, &hi);
-    }
-    int buf = 0, nfix = 0, nseg = 0, nslow = 0, nxo = 0, nqd = 0;   // (nqd: band pairs queued, trace builds)
-    uint64_t tloop = 0, t_total = 0, t_hyp = 0;
-    uint64_t c_stage = 0, c_hot = 0, c_fix = 0, c_seg = 0, c_mark = 0;   // debug: shader cycles per phase
-    uint64_t c_band = 0, c_flush = 0, c_xo = 0;                            // (trace builds: parts of c_fix)
+    even_share(total, nunits, (uint32_t)unit, &lo, &hi);   // (no weighted rounds here: k_vote_count's alone)
+    // (the counters and stamps below: trace builds only read them)
+    int buf = 0;
+    [[maybe_unused]] int nfix = 0, nseg = 0, nslow = 0, nxo = 0, nqd = 0;   // (nqd: band pairs queued, trace builds)
+    [[maybe_unused]] uint64_t tloop = 0, t_total = 0, t_hyp = 0;
+    [[maybe_unused]] uint64_t c_stage = 0, c_hot = 0, c_fix = 0, c_seg = 0, c_mark = 0;   // debug: shader cycles per phase
+    [[maybe_unused]] uint64_t c_band = 0, c_flush = 0, c_xo = 0;                            // (trace builds: parts of c_fix)
     auto cyc = [&]() -> uint64_t { return PVV_TRACE_ON(a) ? __builtin_amdgcn_s_memtime() : 0; };
     if (PVV_TRACE_ON(a)) t_total = __builtin_amdgcn_s_memrealtime();
     const float tau = a.tau;
@@ -847,37 +894,46 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
             }
         };
         load_px(ts, min(kMChunk, te - ts));
-        // hypotheses: lane makes h = hg*128 + i*64 + lane (i = 0, 1), stored at
-        // [set 2i + half][col] -- the same linear index.  The making lane also
-        // classifies it (fast / exact-only), once per hypothesis: bit i and bit
-        // 2 + i of `own` are set 2i + half's two classes of column col, and one
-        // v_permlane32_swap gives every lane both halves' words, i.e. all four
-        // sets' classes of its column (the same predicate on the same value as
-        // a classification of the four sets in every lane)
-        uint32_t own = 0;
+        // hypotheses: lane loads h = hg*128 + i*64 + lane (i = 0, 1) into
+        // [set 2i + half][col] -- the same linear index -- of the wave's LDS row.
+        // Their classes (hyp_class: fast / exact-only) as wave-uniform words,
+        // bit c of wf[j] / wx[j] for column c of set j: the pipeline reads the
+        // ballots that the hypotheses' producer stored with them (two scalar
+        // loads: 85 blocks per keypoint used to classify the same 512 values
+        // again); pv_vote_counts' hypotheses have no producer and are
+        // classified here, two ballots per lane slot (half 0's lanes are set
+        // 2i, half 1's set 2i + 1).  A lane's own class is then its bit of a
+        // mask in scalar registers (inverse ballot), no vector instruction.
+        uint32_t wf[kMSet], wx[kMSet];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int h = hg * kGroup + i * kWave + lane;
             const bool hl = h < a.nh;
-            // pre-generated (k_hyp_gen, a.hyp keypoint-major) or made here
-            const float2 hv = a.hyp ? item_hyp<false, PREPPED>(a, b, v, h, hl, n, false)
-                                    : item_hyp<PREPPED, PREPPED>(a, b, v, h, hl, n, PREPPED && ts == 0);
+            float2 hv = make_float2(0.f, 0.f);
+            if (hl) hv = PREPPED ? a.hyp[((int64_t)b * a.vn + v) * a.nh + h] : a.hyp[(int64_t)h * a.vn + v];
             hlds[i * kWave + lane] = hv;
-            const bool fin = isfinite(hv.x) && isfinite(hv.y);
-            const bool xo = hl && fin &&
-                            (hyp_exact_only(hv.x, hv.y) || !(fabsf(hv.x) < kMHypMax && fabsf(hv.y) < kMHypMax));
-            own |= (hl && fin && !xo) ? 1u << i : 0u;
-            own |= xo ? 4u << i : 0u;
+            if constexpr (!PREPPED) {
+                const uint32_t c = hl ? hyp_class(hv.x, hv.y) : 0u;
+                const uint64_t bf_ = __builtin_amdgcn_ballot_w64((c & kHypFast) != 0);
+                const uint64_t bx_ = __builtin_amdgcn_ballot_w64((c & kHypExact) != 0);
+                wf[2 * i] = (uint32_t)bf_; wf[2 * i + 1] = (uint32_t)(bf_ >> 32);
+                wx[2 * i] = (uint32_t)bx_; wx[2 * i + 1] = (uint32_t)(bx_ >> 32);
+            }
+        }
+        if constexpr (PREPPED) {
+            typedef __attribute__((address_space(4))) const uint32_t cu32;   // constant address space: scalar loads
+            // (a 32-bit word index in scalar registers: launch_vote keeps the launch's words below 2^31)
+            const int ci = uniform(((b * a.vn + v) * (4 * a.hgn) + 4 * hg) * 2);
+            const cu32 *cw = (const cu32 *)(a.hypcls + ci);
+#pragma unroll
+            for (int j = 0; j < kMSet; ++j) { wf[j] = cw[2 * j]; wx[j] = cw[2 * j + 1]; }
         }
         __builtin_amdgcn_wave_barrier();
         // (the exact hypotheses stay in LDS, hlds[set * 32 + col]: read where
         // needed rather than held in registers across the hot loop)
-        // per set: fast / exact-only (bit j); half 0's word holds sets 0 and 2, half 1's sets 1 and 3
-        const auto cls = __builtin_amdgcn_permlane32_swap(own, own, false, false);
-        const uint32_t c02 = cls[0], c13 = cls[1];
-        const uint32_t hfm = (c02 & 1u) | ((c13 & 1u) << 1) | ((c02 & 2u) << 1) | ((c13 & 2u) << 2);
-        const uint32_t hxm = ((c02 >> 2) & 1u) | (((c13 >> 2) & 1u) << 1) | (((c02 >> 2) & 2u) << 1) | (((c13 >> 2) & 2u) << 2);
-        const bool any_xo = __builtin_amdgcn_ballot_w64(hxm != 0) != 0;   // wave-uniform
+        const bool any_xo = (wx[0] | wx[1] | wx[2] | wx[3]) != 0;
+        // is this lane's column of set j a fast hypothesis?  (j a constant)
+        auto fast_col = [&](int j) -> bool { return __builtin_amdgcn_inverse_ballot_w64(both_halves(wf[j])); };
         int cnt[kMSet] = {0, 0, 0, 0};
         corr[lane] = 0;
         corr[64 + lane] = 0;
@@ -1010,7 +1066,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     const int j = 2 * half + i;                           // the set this lane makes
-                    const bool fj = (hfm >> j) & 1u;
+                    const bool fj = __builtin_amdgcn_inverse_ballot_w64((uint64_t)wf[i] | ((uint64_t)wf[2 + i] << 32));
                     float hx, hy, s, Bv;
                     hscale(j, fj, hx, hy, s, Bv);
                     const float hxs = hx * s, hys = hy * s;               // exact
@@ -1087,7 +1143,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                 }
                 // positives = slots - negatives (padding and never-voting rows are negative)
 #pragma unroll
-                for (int j = 0; j < kMSet; ++j) cnt[j] += ((hfm >> j) & 1u) ? 8 * nb - (int)(neg[j] / 255u) : 0;
+                for (int j = 0; j < kMSet; ++j) cnt[j] += fast_col(j) ? 8 * nb - (int)(neg[j] / 255u) : 0;
                 { const uint64_t t = cyc(); c_hot += t - c_mark; c_mark = t; }
                 // ---- band pairs: the same MFMA again (bit-identical); each pair
                 // against its own distance, bounded from the MFMA's own forms:
@@ -1095,7 +1151,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                 // the forms' own errors, < gzm B s, add < 1e-3 of G), and the
                 // reference's sequence inside the band ----
 #ifdef PVV_PROFILE   // ablation bit 64: band pairs keep the sign count's guess (counts wrong)
-                if (a.rw[3] == 7777) hm0 = hm1 = 0;
+                if (a.abl == 7777) hm0 = hm1 = 0;
 #endif
                 // the queued pairs by the reference's sequence, one pair per lane;
                 // a decision the sign count got wrong corrects (set, column)
@@ -1132,11 +1188,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                 // reference's sequence: a superset of round 5's queue, so every
                 // decision still equals KU's.
                 // K, and G' / gb, are functions of tau, gzf and gzr alone: made once on the
-                // host (a.bk, band_consts in pv_band.h: the same float32 expressions)
+                // host (a.gq, a.Kb: band_consts in pv_band.h, the same float32 expressions)
                 float Gs[kMSet];
 #pragma unroll
-                for (int j = 0; j < kMSet; ++j) Gs[j] = gb[j] * a.bk.gq;
-                const float Kb = a.bk.Kb;
+                for (int j = 0; j < kMSet; ++j) Gs[j] = gb[j] * a.gq;
+                const float Kb = a.Kb;
                 // The candidates of flagged MFMA (batch p, set j) are the pairs with fj && pix < np
                 // && ts[q] <= G.  Only ts[q] <= G is a per-lane test; the other two are wave masks
                 // combined with its ballot in scalar registers:
@@ -1151,7 +1207,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                 // lane's part (col, half) plus the wave-uniform part (p, j, the guess as 1) once per
                 // flagged MFMA, off(q) added per entry, and a negative z takes the guess back.
                 auto band_test = [&](const f32x16 &c, int p, int j) {
-                    const uint64_t fmj = __builtin_amdgcn_ballot_w64((hfm >> j) & 1u);
+                    const uint64_t fmj = both_halves(j == 0 ? wf[0] : j == 1 ? wf[1] : j == 2 ? wf[2] : wf[3]);
                     // (selects on the wave-uniform j: a dynamic index would put Gs / bf in scratch)
                     const float G = j == 0 ? Gs[0] : j == 1 ? Gs[1] : j == 2 ? Gs[2] : Gs[3];
                     float zs[8], ts[8];
@@ -1166,7 +1222,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                     mt = __builtin_elementwise_minimum(__builtin_elementwise_minimum(mt, ts[5]), ts[6]);
                     mt = __builtin_elementwise_minimum(mt, ts[7]);
 #ifdef PVV_PROFILE   // ablation bit 128: the candidates found but never queued (counts wrong)
-                    if (a.rw[3] == 7778) mt = 3.0e38f;
+                    if (a.abl == 7778) mt = 3.0e38f;
 #endif
                     if ((__builtin_amdgcn_ballot_w64(mt <= G) & fmj) != 0) {
                         const int rem = np - p * kMB;
@@ -1228,7 +1284,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                 // sets' ballots): lane = pixel, one hypothesis at a time
 #pragma unroll
                 for (int j = 0; any_xo && j < kMSet; ++j) {
-                    uint64_t mm = __builtin_amdgcn_ballot_w64(((hxm >> j) & 1u) && half == 0);
+                    uint64_t mm = wx[j];   // (half 0's lanes: one lane per column)
                     nxo += __popcll(mm);
                     while (mm) {
                         const int l = __builtin_ctzll(mm);
@@ -1257,7 +1313,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
                     const F4 e = S.x.get(jj);
 #pragma unroll
                     for (int j = 0; j < kMSet; ++j)
-                        if ((hfm | hxm) >> j & 1u) {
+                        if (__builtin_amdgcn_inverse_ballot_w64(both_halves(wf[j] | wx[j]))) {
                             const float2 hv = hlds[j * 32 + col];
                             cnt[j] += exact_vote(e.z, e.w, e.x, e.y, hv.x, hv.y, a.thr);
                         }
@@ -1269,18 +1325,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int j = 0; j < kMSet; ++j) cnt[j] += half == 0 ? corr[j * 32 + col] : 0;
-        int32_t *cp = a.counts + (int64_t)b * a.cnt_bs + (int64_t)v * a.cnt_v;
 #pragma unroll
         for (int j = 0; j < kMSet; ++j) {
             const auto sw = __builtin_amdgcn_permlane32_swap(cnt[j], cnt[j], false, false);
             const int tot = (int)(sw[0] + sw[1]);   // both halves, VALU only
             const int h = hg * kGroup + j * 32 + col;
-            if (half == 0 && h < a.nh && tot) atomicAdd(&cp[(int64_t)h * a.cnt_h], tot);
+            if (half == 0 && h < a.nh && tot)
+                atomicAdd(PREPPED ? &a.counts[((int64_t)b * a.vn + v) * a.nh + h] : &a.counts[(int64_t)h * a.vn + v], tot);
         }
         lo += te - ts;
         ++nseg;
         { const uint64_t t = cyc(); c_fix += t - c_mark; c_mark = t; }
     }
+#ifdef PVV_TRACE
     if (PVV_TRACE_ON(a) && lane == 0) {
         const int wave = (int)(blockIdx.x * 4 + wid);
         uint64_t *q = a.trace + 65536 + wave * 8;
@@ -1301,6 +1358,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVM_WPE, PV
         a.trace[wave * 8 + 6] = t_total;
         a.trace[wave * 8 + 7] = t_hyp;
     }
+#endif
 }
 
 // The matrix-core vote (k_vote_mfma): its own fast-path constant (DESIGN.md
@@ -1345,23 +1403,48 @@ uint64_t *g_vote_trace = nullptr;   // trace builds only (pv_debug_set_vote_trac
 std::atomic<int> g_vote_kernel{0};   // 0: k_vote_mfma (hn a multiple of 512), 1: k_vote_count
 bool vote_old() { return g_vote_kernel.load(std::memory_order_relaxed) == 1; }
 
+// k_vote_mfma's arguments from the launch's VoteArgs (va.hyp set)
 template <bool PREPPED>
-void launch_vote(const VoteArgs &va, int64_t pixel_steps, hipStream_t s) {
+MVoteArgs<PREPPED> mvote_args(const VoteArgs &va) {
+    MVoteArgs<PREPPED> m{};
+    if constexpr (PREPPED) {
+        m.pex = va.pex; m.hypcls = va.hypcls;
+    } else {
+        m.coords = va.coords; m.raw = va.raw; m.raw_v = va.raw_v; m.raw_t = va.raw_t;
+    }
+    m.hyp = va.hyp; m.counts = va.counts; m.tn_dev = va.tn_dev;
+    m.P = va.P; m.tn_host = va.tn_host; m.b = va.b; m.vn = va.vn; m.nh = va.nh; m.hgn = va.hgn; m.fast = va.fast;
+    m.thr = va.thr; m.tau = va.tau; m.gzr = va.gzr;
+    m.gzf = va.fast ? mfma_gz(va.tau) : 0.f;
+    // (!fast: tau = 0, every sub-chunk takes the slow path and reads none of them)
+    const BandConsts bk = va.fast ? band_consts(m.tau, m.gzf, m.gzr) : BandConsts{};
+    m.gq = bk.gq; m.Kb = bk.Kb;
+#ifdef PVV_PROFILE
+    m.abl = (g_abl & 64) ? 7777 : (g_abl & 128) ? 7778 : 0;
+#endif
+#ifdef PVV_TRACE
+    m.trace = va.trace;
+#endif
+    return m;
+}
+
+// (int: PV_EINVAL for a launch k_vote_mfma cannot take, nothing launched; launch errors are the caller's last())
+template <bool PREPPED>
+int launch_vote(const VoteArgs &va, int64_t pixel_steps, hipStream_t s) {
     if (va.hgn % 4 == 0 && !vote_old()) {
+        // k_vote_mfma makes no hypotheses: it needs them made (and, in the pipeline, classified) before it,
+        // in the layout its instantiation reads
+        if (!va.hyp || (PREPPED ? !va.hypcls || va.hyp_sb != (int64_t)va.vn * va.nh || va.hyp_sv != va.nh ||
+                                      va.hyp_sh != 1 || va.cnt_bs != va.vn * va.nh || va.cnt_v != va.nh || va.cnt_h != 1
+                                : va.b != 1 || va.hyp_sv != 1 || va.hyp_sh != va.vn || va.cnt_v != 1 || va.cnt_h != va.vn))
+            return PV_EINVAL;
+        if (PREPPED && (int64_t)va.b * va.vn * hyp_sets(va.nh) * 2 >= (1ll << 31)) return PV_EINVAL;   // the class words' 32-bit index
         // blocks per CU of the persistent grid: with 3 of the 4 wave slots
         // of every SIMD one launch leaves room for the next image's blocks,
         // whose prologue (dependent loads) then overlaps this one's
         // matrix/VALU work; the work is cut evenly over the blocks
         const int grid = vote_grid_steps(pixel_steps, (const void *)k_vote_mfma<PREPPED>, PVV_VM_BPC);
-        VoteArgs vr = va;
-        vr.gzf = va.fast ? mfma_gz(va.tau) : 0.f;
-        // (!fast: tau = 0, every sub-chunk takes the slow path and reads none of them)
-        vr.bk = va.fast ? band_consts(vr.tau, vr.gzf, vr.gzr) : BandConsts{};
-        for (int k = 0; k < 4; ++k) vr.rw[k] = 0;
-        // (rw[3]: the sentinels of k_vote_mfma's two band ablations, profiling builds)
-        if (g_abl & 128) vr.rw[3] = 7778;
-        if (g_abl & 64) vr.rw[3] = 7777;
-        k_vote_mfma<PREPPED><<<grid, 256, 0, s>>>(vr);
+        k_vote_mfma<PREPPED><<<grid, 256, 0, s>>>(mvote_args<PREPPED>(va));
     } else if (va.hgn % 4 == 0) {
         const int grid = vote_grid_steps(pixel_steps, (const void *)k_vote_count<PREPPED, true>, 4);
         VoteArgs vr = va;
@@ -1377,6 +1460,7 @@ void launch_vote(const VoteArgs &va, int64_t pixel_steps, hipStream_t s) {
     } else
         k_vote_count<PREPPED, false>
             <<<vote_grid_steps(pixel_steps, (const void *)k_vote_count<PREPPED, false>), 256, 0, s>>>(va);
+    return PV_OK;
 }
 
 }  // namespace
@@ -1422,13 +1506,13 @@ void launch_hyp_gen(const VoteArgs &va, hipStream_t s) {
 #endif
 }
 
-void launch_pipeline_vote(const VoteArgs &va, int64_t pixel_steps, hipStream_t s) {
+int launch_pipeline_vote(const VoteArgs &va, int64_t pixel_steps, hipStream_t s) {
 #ifdef PVV_TRACE
     VoteArgs vt = va;
     vt.trace = g_vote_trace;
-    launch_vote<true>(vt, pixel_steps, s);
+    return launch_vote<true>(vt, pixel_steps, s);
 #else
-    launch_vote<true>(va, pixel_steps, s);
+    return launch_vote<true>(va, pixel_steps, s);
 #endif
 }
 
@@ -1454,8 +1538,8 @@ int pv_vote_counts(const float *direct, const float *coords, const float *hypo, 
     fast_constants(inlier_thresh, &va);
     if (tn == 0) return PV_OK;
     if ((int64_t)vn * va.hgn * tn >= (1ll << 31)) return PV_EINVAL;   // the kernel's 32-bit work index
-    launch_vote<false>(va, (int64_t)vn * va.hgn * tn, s);
-    return last();
+    const int r = launch_vote<false>(va, (int64_t)vn * va.hgn * tn, s);
+    return r ? r : last();
 }
 
 #ifdef PVV_TRACE
