@@ -178,7 +178,9 @@ typedef struct pv_aug_desc {
 } pv_aug_desc;
 
 /* Bytes of workspace of pv_augment_apply with PV_AUG_CONTRAST for these sizes; 0 for bad sizes.
- * The workspace is 256-byte aligned device memory, owned by the call until it has run. */
+ * The workspace is 256-byte aligned device memory, owned by the call until it has run.  It need
+ * not be cleared: the first pass writes every partial the second reads, and the call writes nothing
+ * but its two outputs and workspace[0, size). */
 size_t pv_augment_workspace_size(int32_t b, int32_t Ho, int32_t Wo);
 
 /* stats: i64 [b][8], 8-byte aligned. */

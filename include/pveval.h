@@ -109,7 +109,8 @@ typedef struct pv_eval_batch {
  * return).  A pose (or, for the projection columns, a K) with a NaN or infinite entry gets NaN in
  * every requested column.  A column whose metric was not requested is left untouched.
  * No float atomics: per-block partial sums go to the workspace and a second launch adds them in
- * block order, so `out` is bit-identical from run to run. */
+ * block order, so `out` is bit-identical from run to run.  The workspace need not be cleared: the
+ * call writes every partial it reads, and writes nothing but `out` and workspace[0, size). */
 size_t pv_eval_workspace_size(int32_t b, int32_t max_pn);   /* host only; 0 for b < 1 or max_pn < 0 */
 int pv_pose_metrics(const pv_eval_batch *batch /* host */, double *out, void *workspace, size_t workspace_bytes,
                     pv_stream_t stream);

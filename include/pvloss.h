@@ -140,7 +140,8 @@ typedef struct pv_loss_grad {
 
 /* Bytes of workspace of pv_loss_forward for these sizes; 0 for bad sizes.  The workspace is 256-byte
  * aligned device memory, owned by the call until it has run.  pv_loss_backward reduces nothing and
- * takes none. */
+ * takes none.  The workspace need not be cleared: the forward writes every partial it reads, and
+ * writes nothing but its outputs and workspace[0, size). */
 size_t pv_loss_workspace_size(int32_t b, int32_t H, int32_t W, int32_t ncls);
 
 /* At least one of desc->seg and desc->vertex.  With seg absent loss_seg and counts are not written,

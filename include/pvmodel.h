@@ -78,7 +78,9 @@ typedef struct pv_model_points {
 
 /* Bytes of workspace for any of the calls below on a table of these sizes; pass k = 1 for a call
  * that takes no k.  0 for bad sizes (negative, or k outside 1..PV_MODEL_MAX_K).  The workspace is
- * 256-byte aligned device memory, owned by the call until it has run. */
+ * 256-byte aligned device memory, owned by the call until it has run.  It need not be cleared: a
+ * call initialises every accumulator and slot it reads, and writes nothing but its outputs and
+ * workspace[0, size). */
 size_t pv_model_workspace_size(int32_t nmodels, int32_t total, int32_t k);
 
 /* ---- 1. pv_model_extent ---------------------------------------------------------------------------

@@ -133,7 +133,8 @@ typedef struct pv_render_out { /* any may be NULL, but not all of label, inst an
 size_t pv_render_workspace_size(int32_t b, int32_t H, int32_t W, int64_t total_iv, int32_t total_inst);
 
 /* workspace: 256-byte aligned device memory of at least pv_render_workspace_size(...) bytes,
- * owned by the call until it has run. */
+ * owned by the call until it has run.  It need not be cleared: the call initialises every key,
+ * record and count it reads, and writes nothing but its outputs and workspace[0, size). */
 int pv_render_labels(const pv_render_meshes *meshes /* host */, const pv_render_batch *batch /* host */,
                      const pv_render_out *out /* host */, void *workspace, size_t workspace_bytes,
                      pv_stream_t stream);

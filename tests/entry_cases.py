@@ -241,17 +241,19 @@ def field_is_half(layout):
     return layout.startswith("f16")
 
 
-def field_tensor(layout, ver, device):
+def field_tensor(layout, ver, device, place=None):
     """(view [b,H,W,CH,2], the tensor that owns its memory) of the f32 field ``ver`` in a layout.
     Cropped and placed views sit in NaN-filled allocations: "_in" with padding rows, columns and
     channels on every side, "_end" with padding in front only, so that the view's last element is
-    the allocation's last."""
+    the allocation's last.  ``place``: numpy array -> the device tensor that owns it (default: a copy
+    to ``device``)."""
     import torch
     b, H, W, CH, _ = ver.shape
     dt = np.float16 if field_is_half(layout) else np.float32
 
     def dev(a):
-        return torch.from_numpy(np.array(a, order="C")).to(device)          # a copy: the case's inputs stay read-only
+        a = np.array(a, order="C")                                          # a copy: the case's inputs stay read-only
+        return torch.from_numpy(a).to(device) if place is None else place(a)
     if layout == "f32_nhwc":
         t = dev(ver)
         return t, t
@@ -277,16 +279,17 @@ def field_tensor(layout, ver, device):
     raise ValueError(layout)
 
 
-def mask_tensor(kind, arr, device):
+def mask_tensor(kind, arr, device, place=None):
     """(view, owner): ``arr`` is the label map [b,H,W] in the kind's dtype, or logits [b,C,H,W].
     i64: dense; i32: a cropped view whose row stride is above W; u8: a transposed-memory view;
     seg_f32: channels-last memory; seg_f16: a cropped NCHW view.
     The int32 view's padding holds label 1 and the f16 logits' padding NaN: a read outside the
-    view changes the result."""
+    view changes the result.  ``place``: as field_tensor's."""
     import torch
 
     def dev(a):
-        return torch.from_numpy(np.array(a, order="C")).to(device)          # a copy: the case's inputs stay read-only
+        a = np.array(a, order="C")                                          # a copy: the case's inputs stay read-only
+        return torch.from_numpy(a).to(device) if place is None else place(a)
     if kind == "i64":
         t = dev(arr)
         return t, t

@@ -87,68 +87,93 @@ def class_words(hyp, nh):
     return out
 
 
-def device_inputs(case, device):
+def device_inputs(case, device, place=None):
     inp = EC.inputs(case)
-    mask, _ = EC.mask_tensor(case.kind, inp["mask"], device)
-    field, owner = EC.field_tensor(case.field, inp["field"], device)
+    mask, _ = EC.mask_tensor(case.kind, inp["mask"], device, place)
+    field, owner = EC.field_tensor(case.field, inp["field"], device, place)
     return inp, mask, field, owner
 
 
-def run(case, device, rvg, draws="inject"):
+class TorchBuffers:
+    """run()'s default allocator: inputs copied to the device, outputs from torch.empty / torch.full, the
+    workspace a fresh VotingWorkspace's buffer filled with 0xA5.  Another allocator (the guarded buffers of
+    tests/test_gpu_memory_contract.py) has the same five methods."""
+
+    def __init__(self, device, rvg):
+        self.device, self.ws = device, rvg.VotingWorkspace()
+
+    def inp(self, a):
+        return cu(a, self.device)
+
+    def empty(self, shape, dtype):
+        return torch.empty(shape, dtype=dtype, device=self.device)
+
+    def full(self, shape, value, dtype):
+        return torch.full(shape, value, dtype=dtype, device=self.device)
+
+    def workspace(self, nbytes):
+        buf = self.ws.get(self.device, nbytes)
+        buf.fill_(0xA5)                                         # nothing the call reads is its own leftover
+        return buf
+
+    def done(self):
+        self.ws.done(self.device)
+
+
+def run(case, device, rvg, draws="inject", alloc=None):
     """The case through its C entry.  ``draws``: "inject" hands the case's pairs and keep mask in,
-    "seed" leaves both to the call's RNG.  -> dict of numpy arrays with leading [bv]."""
-    inp, mask, field, _ = device_inputs(case, device)
+    "seed" leaves both to the call's RNG.  ``alloc``: where the buffers come from (TorchBuffers).
+    -> dict of numpy arrays with leading [bv]."""
+    alloc = alloc or TorchBuffers(device, rvg)
+    inp, mask, field, _ = device_inputs(case, device, alloc.inp)
     seg = case.kind in EC.SEG
     d = rvg._desc(mask, field, seg=seg) if case.ncls == 0 else rvg._desc_multi(mask, field, case.ncls, seg=seg)
     assert (d.b, d.H, d.W, d.vn, d.ncls) == (case.b, case.H, case.W, case.vn, case.ncls)
     bv, vn, nh = case.bv, case.vn, case.nh
     inject = draws == "inject"
-    idxs = cu(inp["idxs"], device) if inject else None
-    keep = cu(inp["keep"], device) if inject and inp["keep"] is not None else None
+    idxs = alloc.inp(inp["idxs"]) if inject else None
+    keep = alloc.inp(inp["keep"]) if inject and inp["keep"] is not None else None
     evd = case.entry.startswith("evd")
     rhn = case.rounds[0]
     prm = rvg._params(rhn, case.thresh, 0.99, 20 if case.entry == "v5" else 100, inp["min_num"], inp["max_num"], case.seed,
                       idxs, keep, min_hyp_num=nh if evd else 0, topk=case.topk if case.entry == "evd_topk" else 0)
     L = _lib.load()
     nbytes = L.pv_v3_workspace_size(bv, case.H, case.W, vn, nh)
-    ws = rvg.VotingWorkspace()
-    buf = ws.get(device, nbytes)
-    buf.fill_(0xA5)                                             # nothing the call reads is its own leftover
+    buf = alloc.workspace(nbytes)
     stream = torch.cuda.current_stream(device).cuda_stream
-    f32 = dict(dtype=torch.float32, device=device)
-    i32 = dict(dtype=torch.int32, device=device)
+    f32, i32 = torch.float32, torch.int32
     out = {}
     with torch.cuda.device(device):
         try:
             if not evd:
-                dt = dict(hyp=torch.empty((bv, nh, vn, 2), **f32), counts=torch.empty((bv, vn, nh), **i32),
-                          win_idx=torch.empty((bv, vn), **i32), win_ratio=torch.empty((bv, vn), **f32),
-                          tn=torch.empty(bv, **i32), iters=torch.empty(bv, **i32), ata=torch.empty((bv, vn, 2, 2), **f32),
-                          atb=torch.empty((bv, vn, 2), **f32))
+                dt = dict(hyp=alloc.empty((bv, nh, vn, 2), f32), counts=alloc.empty((bv, vn, nh), i32),
+                          win_idx=alloc.empty((bv, vn), i32), win_ratio=alloc.empty((bv, vn), f32),
+                          tn=alloc.empty((bv,), i32), iters=alloc.empty((bv,), i32), ata=alloc.empty((bv, vn, 2, 2), f32),
+                          atb=alloc.empty((bv, vn, 2), f32))
                 diag = _lib.V3Diag(**{k: v.data_ptr() for k, v in dt.items()})
-                kp = torch.full((bv, vn, 2), np.nan, **f32)
+                kp = alloc.full((bv, vn, 2), np.nan, f32)
                 if case.entry == "v3":
                     code = L.pv_ransac_voting_v3(ctypes.byref(d), ctypes.byref(prm), kp.data_ptr(), buf.data_ptr(), nbytes,
                                                  ctypes.byref(diag), stream)
                 else:
-                    conf = torch.full((bv, vn), np.nan, **f32)
+                    conf = alloc.full((bv, vn), np.nan, f32)
                     code = L.pv_ransac_voting_v5(ctypes.byref(d), ctypes.byref(prm), 0.999, kp.data_ptr(), conf.data_ptr(),
                                                  buf.data_ptr(), nbytes, ctypes.byref(diag), stream)
                     out["conf"] = conf
                 out.update(dt, kp=kp)
             else:
-                cov = torch.full((bv, vn, 2, 2), np.nan, **f32)
+                cov = alloc.full((bv, vn, 2, 2), np.nan, f32)
                 if case.entry == "evd_mean":
-                    mean = cu(inp["mean"], device)
+                    mean = alloc.inp(inp["mean"])
                     code = L.pv_estimate_voting_distribution_with_mean(ctypes.byref(d), ctypes.byref(prm), mean.data_ptr(),
                                                                        cov.data_ptr(), buf.data_ptr(), nbytes, stream)
                 else:
-                    mean = torch.full((bv, vn, 2), np.nan, **f32)
+                    mean = alloc.full((bv, vn, 2), np.nan, f32)
                     code = L.pv_estimate_voting_distribution(ctypes.byref(d), ctypes.byref(prm), mean.data_ptr(),
                                                              cov.data_ptr(), buf.data_ptr(), nbytes, stream)
                 out.update(mean=mean, cov=cov)
         finally:
-            ws.done(device)
+            alloc.done()
     _lib.check(code, case.name)
     out = {k: v.cpu().numpy() for k, v in out.items()}
     words, counts, tn, hyp = workspace_views(buf, nbytes, bv, case.H, case.W, vn, nh)
