@@ -49,6 +49,12 @@ typedef void *pv_stream_t; /* hipStream_t */
  *      Under keypoint noise the pose depends on this sign (1e-4 in the median at 1 px, far more
  *      in rare cases), so parity with
  *      cv2 is algorithmic (exact on exact data), not bitwise.
+ *      REPEATED EIGENVALUES (a cube, a box with a square section, a can: the box corners and
+ *      farthest points the product uses as keypoints): the axes inside the eigenspace are whatever
+ *      the cyclic 3x3 Jacobi solver returns for this covariance, a dependence of the same kind as
+ *      the sign.  EPnP is exact for any non-degenerate control basis, so the pose is exact on exact
+ *      data; under noise it depends on the basis (another orthonormal basis of the eigenspace
+ *      moves it by up to 0.3 at 1 to 3 px and is as close to the truth in the rms).
  *   2. Barycentric coordinates alpha of every model point, from inv([c1-c0 c2-c0 c3-c0]).
  *   3. M [2 pn][12]: point i, control point j gives (alpha_ij fu, 0, alpha_ij (uc - u_i)) and
  *      (0, alpha_ij fv, alpha_ij (vc - v_i)); v1..v4 = the eigenvectors of M^T M with the four
@@ -70,6 +76,14 @@ typedef void *pv_stream_t; /* hipStream_t */
  *      (planar or collinear model), or when the chosen candidate's error or any value of its
  *      pose is not finite (NaN / Inf keypoints; keypoints that all coincide, as the all-zero
  *      keypoints of an absent class do).
+ *      THIN MODELS: on exact projections every candidate is the true cloud, whose Arun matrix has
+ *      singular values that scale like the PCA eigenvalues, so step 7's 1e-10 decides before the
+ *      1e-12 here: a model whose eigenvalue ratio is below about 1e-10 loses all three candidates
+ *      and is DEGENERATE (OK and exact at a ratio >= 1e-9, DEGENERATE at <= 1e-11, either between).
+ *      Keypoint noise lifts the candidates off their plane: at a ratio of 1e-11, noise of
+ *      0.001 px leaves four images in five DEGENERATE, 0.01 px one in five, 1 px none.  At 1 px
+ *      only the 1e-12 planar gate is left: OK at 1e-11, DEGENERATE at 1e-13.  In between (0.003 to
+ *      0.3 px) about one image in 400 loses one or two candidates to step 7 and another wins.
  * pn >= 6: with fewer points 2 pn < 12 and M^T M's null space has more than one dimension
  * whatever the data, so the result would depend on the eigen solver's choice of basis.
  * Sums over the points run in index order; two runs on the same input are bit-equal. */

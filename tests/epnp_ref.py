@@ -87,17 +87,34 @@ def _lstsq(A, b):
     return np.linalg.lstsq(A, b, rcond=None)[0]
 
 
-def betas_approx(n, L, rho):
-    """Step 5: cv2's find_betas_approx_1/2/3."""
+def _trace_start(n, x):
+    """The sign and zero rules of step 5 on the solution x of start n, and each rule's distance from its
+    threshold (zero) relative to max |x|.  N = 1 has the sign of x[0] only."""
+    with np.errstate(all="ignore"):
+        sc = float(np.abs(x).max())
+        rel = (lambda v: float(abs(v) / sc)) if sc > 0 and np.isfinite(sc) else (lambda v: 0.0)
+        t = dict(x0_neg=bool(x[0] < 0), x0_margin=rel(x[0]), x2_zero=None, x2_margin=None, x1_neg=None, x1_margin=None)
+        if n > 1:
+            t.update(x2_zero=not bool(x[2] < 0 if x[0] < 0 else x[2] > 0), x2_margin=min(rel(x[0]), rel(x[2])),
+                     x1_neg=bool(x[1] < 0), x1_margin=rel(x[1]))
+    return t
+
+
+def betas_approx(n, L, rho, trace=None):
+    """Step 5: cv2's find_betas_approx_1/2/3.  `trace` (a dict) receives _trace_start's record."""
     with np.errstate(all="ignore"):
         be = np.zeros(4)
         if n == 1:
             x = _lstsq(L[:, [0, 1, 3, 6]], rho)
+            if trace is not None:
+                trace.update(_trace_start(n, x))
             be[0] = np.sqrt(abs(x[0]))
             s = -1.0 if x[0] < 0 else 1.0
             be[1:] = s * x[1:] / be[0]
             return be
         x = _lstsq(L[:, :3] if n == 2 else L[:, :5], rho)
+        if trace is not None:
+            trace.update(_trace_start(n, x))
         be[0] = np.sqrt(abs(x[0]))
         if x[0] < 0:
             be[1] = np.sqrt(-x[2]) if x[2] < 0 else 0.0
@@ -129,14 +146,21 @@ def gauss_newton(L, rho, be, iters=5):
     return be
 
 
-def candidate_pose(be, v, alphas, p3, p2, K):
-    """Step 7 -> (R, t, mean reprojection error in px)."""
+def candidate_pose(be, v, alphas, p3, p2, K, trace=None):
+    """Step 7 -> (R, t, mean reprojection error in px).  `trace` (a dict) receives the candidate's
+    decisions, each with its distance from the threshold: `negated` (point 0 behind the camera;
+    |z of point 0| over the largest |coordinate| of the cloud), `rank_reject` (|s2 - 1e-10 s0| over
+    1e-10 s0) and `det_flip` (|det R|, which is 1 for any R that passed the rank gate)."""
     nanpose = (np.full((3, 3), np.nan), np.full(3, np.nan))
+    if trace is not None:
+        trace.update(negated=None, z0_margin=None, rank_reject=None, rank_margin=None, det_flip=None, det_margin=None)
     if not np.isfinite(be).all():
         return (*nanpose, np.nan)
     with np.errstate(all="ignore"):
         ccs = (be @ v).reshape(4, 3)
         pcs = alphas @ ccs
+        if trace is not None:
+            trace.update(negated=bool(pcs[0, 2] < 0), z0_margin=float(abs(pcs[0, 2]) / np.abs(pcs).max()))
         if pcs[0, 2] < 0:
             ccs, pcs = -ccs, -pcs
         pn = p3.shape[0]
@@ -145,9 +169,14 @@ def candidate_pose(be, v, alphas, p3, p2, K):
         if not np.isfinite(ABt).all():
             return (*nanpose, np.nan)
         U, s, Vt = np.linalg.svd(ABt)
+        if trace is not None:
+            trace.update(rank_reject=not bool(s[2] > RANK_RATIO * s[0]),
+                         rank_margin=float(abs(s[2] - RANK_RATIO * s[0]) / (RANK_RATIO * s[0])) if s[0] > 0 else 0.0)
         if not s[2] > RANK_RATIO * s[0]:
             return (*nanpose, np.inf)
         R = U @ Vt
+        if trace is not None:
+            trace.update(det_flip=bool(np.linalg.det(R) < 0), det_margin=float(abs(np.linalg.det(R))))
         if np.linalg.det(R) < 0:
             R[2] = -R[2]
         t = pc0 - R @ pw0
@@ -173,13 +202,20 @@ def _degenerate(n_used=1, cand_err=None):
                 n_used=n_used, cand_err=np.full(3, np.nan) if cand_err is None else cand_err)
 
 
-def epnp(p3, p2, K, eigh=eigh_lapack, sign=+1):
-    """points_3d [pn, 3], points_2d [pn, 2], K [3, 3] -> dict(Rt [3, 4], rt6 [6], status, n_used, cand_err [3])."""
+def epnp(p3, p2, K, eigh=eigh_lapack, sign=+1, trace=None):
+    """points_3d [pn, 3], points_2d [pn, 2], K [3, 3] -> dict(Rt [3, 4], rt6 [6], status, n_used, cand_err [3]).
+
+    `trace`, a dict, is filled with this image's decisions (the results do not depend on it):
+    "pca" (the eigenvalues, descending), "starts" and "cands" (one dict per N = 1, 2, 3, see
+    _trace_start and candidate_pose; empty when the image is degenerate before step 5), "n_used",
+    "cand_err" and "select_margin" (second-best minus best candidate error)."""
     p3 = np.asarray(p3, np.float64)
     p2 = np.asarray(p2, np.float64)
     K = np.asarray(K, np.float64)
     assert p3.shape[0] == p2.shape[0] >= 6
     cws, w = control_points(p3, eigh, sign)
+    if trace is not None:
+        trace.update(pca=w.copy(), starts=[], cands=[], n_used=1, cand_err=np.full(3, np.nan), select_margin=np.nan)
     if not w[2] > PLANAR_RATIO * w[0]:
         return _degenerate()
     alphas = barycentric(p3, cws)
@@ -193,11 +229,19 @@ def epnp(p3, p2, K, eigh=eigh_lapack, sign=+1):
     L, rho = build_L_rho(v, cws)
     cands, errs = [], np.empty(3)
     for n in (1, 2, 3):
-        be = gauss_newton(L, rho, betas_approx(n, L, rho))
-        R, t, e = candidate_pose(be, v, alphas, p3, p2, K)
+        ts, tc = (None, None) if trace is None else ({}, {})
+        be = gauss_newton(L, rho, betas_approx(n, L, rho, ts))
+        R, t, e = candidate_pose(be, v, alphas, p3, p2, K, tc)
         cands.append((R, t))
         errs[n - 1] = e
+        if trace is not None:
+            trace["starts"].append(ts)
+            trace["cands"].append(tc)
     n = select(errs)
+    if trace is not None:
+        with np.errstate(all="ignore"):
+            srt = np.sort(errs)
+            trace.update(n_used=n, cand_err=errs.copy(), select_margin=float(srt[1] - srt[0]))
     R, t = cands[n - 1]
     if not (np.isfinite(errs[n - 1]) and np.isfinite(R).all() and np.isfinite(t).all()):
         return _degenerate(n, errs)

@@ -1,6 +1,8 @@
 """pv_epnp's arithmetic without a device: pvnet_amd/csrc/pvepnp_core.h compiled for the host
 (tests/epnp_host.cpp; the kernel's lane phases become loops over the lanes) against tests/epnp_ref.py,
-on the cases and at the tolerance of the device test (tests/test_gpu_epnp.py)."""
+on the cases and at the tolerance of the device test (tests/test_gpu_epnp.py), and on the edge
+families of tests/epnp_cases.py at the gates DESIGN 10c sets for them."""
+import collections
 import ctypes
 import os
 import shutil
@@ -9,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import epnp_cases as C
 from tests import epnp_ref as E
 from tests.test_pnp_oracle import K_LM
 
@@ -17,12 +20,12 @@ TOL = 1e-7
 IDENT = np.concatenate([np.eye(3), np.zeros((3, 1))], 1)
 
 
-@pytest.fixture(scope="module")
-def host(tmp_path_factory):
+def build_host_form(directory):
+    """Compile tests/epnp_host.cpp into `directory` -> run(p3, p2 (f64 or f32), K) -> dict."""
     from pvnet_amd import build
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     cxx = [cxx] if cxx else [build.hipcc(), "-x", "c++"]      # hipcc's clang compiles plain C++ too
-    so = str(tmp_path_factory.mktemp("epnp_host") / "libpvepnp_host.so")
+    so = os.path.join(str(directory), "libpvepnp_host.so")
     subprocess.check_call([*cxx, "-O1", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-o", so,
                            os.path.join(REPO, "tests", "epnp_host.cpp")])
     f = ctypes.CDLL(so).pv_epnp_host
@@ -40,6 +43,11 @@ def host(tmp_path_factory):
                ctypes.addressof(n))
         return dict(Rt=Rt, rt6=rt6, cand_err=ce, n_used=n.value, status=st)
     return run
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    return build_host_form(tmp_path_factory.mktemp("epnp_host"))
 
 
 @pytest.mark.parametrize("pn", [6, 7, 9, 21, 63, 64])
@@ -83,3 +91,43 @@ def test_host_form_degenerate_inputs(host):
         assert h["status"] == E.DEGENERATE and E.epnp(m, q.astype(np.float64), K_LM)["status"] == E.DEGENERATE, what
         np.testing.assert_array_equal(h["Rt"], IDENT)
         np.testing.assert_array_equal(h["rt6"], np.zeros(6))
+
+
+# ---------------------------------------------------------------------------- the edge families (tests/epnp_cases.py)
+def host_results(host, name):
+    f = C.family(name)
+    return [host(f["p3"][i], f["p2"][i], f["K"][i]) for i in range(len(f["p3"]))]
+
+
+@pytest.mark.parametrize("name", C.ALL_FAMILIES)
+def test_host_form_on_the_edge_families(name, host):
+    """C.check_family: exact data against the truth (1e-9) wherever the model is above the thin band;
+    separated eigenvalues against the reference image by image (TOL, or max(TOL, 100 d) where the
+    reference resolves no better), n_used where the reference's candidates are apart, +inf equal to
+    +inf only; repeated eigenvalues under noise by the rms gate (the reference's basis in the
+    eigenspace is LAPACK's, so no image-by-image comparison exists); the thin models' status and the
+    degenerate answer bit for bit; the rotation vector in the theta family."""
+    m = C.check_family(name, host_results(host, name))
+    print(f"{name}: " + ", ".join(f"{k} {v:.2e}" if "ratio" not in k else f"{k} {v:.3f}" for k, v in m.items()))
+
+
+def test_host_form_n_used_comparisons_are_not_empty(host):
+    """Every winner N = 1, 2, 3 was compared with the reference's in at least 3 images, and a
+    candidate at +inf with another one winning in at least 3."""
+    count = collections.Counter()
+    inf_and_winner = 0
+    for name in C.ALL_FAMILIES:
+        if C.is_repeated(name):
+            continue
+        gate = C.gates(name)
+        got = host_results(host, name)
+        for i, (r, _) in enumerate(C.traces(name)):
+            s = np.sort(r["cand_err"])
+            if r["status"] == E.OK and s[1] - s[0] > max(1e-9 * s[1], gate[i]):
+                assert got[i]["n_used"] == r["n_used"]
+                count[r["n_used"]] += 1
+                if np.isinf(r["cand_err"]).any():
+                    np.testing.assert_array_equal(np.isinf(got[i]["cand_err"]), np.isinf(r["cand_err"]))
+                    inf_and_winner += 1
+    print(f"n_used compared: N=1 {count[1]}, N=2 {count[2]}, N=3 {count[3]}; with a candidate at +inf {inf_and_winner}")
+    assert min(count[1], count[2], count[3]) >= 3 and inf_and_winner >= 3
