@@ -109,9 +109,10 @@
 extern "C" {
 #endif
 
-/* The stream type and the return codes are those of the other six headers, whose guards do not
- * know this one: in a translation unit that includes several, include pvaugment.h last. */
-#if !defined(PVVOTE_H_) && !defined(PVEVAL_H_) && !defined(PVPOSE_H_) && !defined(PVRENDER_H_) && !defined(PVMODEL_H_) && !defined(PVLOSS_H_)
+/* The stream type and the return codes: the same block under the same guard in every public header
+ * of this project, so they can be included together in any order. */
+#ifndef PV_STATUS_
+#define PV_STATUS_
 typedef void *pv_stream_t; /* hipStream_t */
 
 #define PV_OK 0

@@ -26,7 +26,10 @@
 extern "C" {
 #endif
 
-#ifndef PVVOTE_H_
+/* The stream type and the return codes: the same block under the same guard in every public header
+ * of this project, so they can be included together in any order. */
+#ifndef PV_STATUS_
+#define PV_STATUS_
 typedef void *pv_stream_t; /* hipStream_t */
 
 #define PV_OK 0

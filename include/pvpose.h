@@ -27,9 +27,10 @@
 extern "C" {
 #endif
 
-/* The stream type and the return codes are those of pvvote.h and pveval.h, whose guards know only
- * each other: in a translation unit that includes several of these headers, include pvpose.h last. */
-#if !defined(PVVOTE_H_) && !defined(PVEVAL_H_)
+/* The stream type and the return codes: the same block under the same guard in every public header
+ * of this project, so they can be included together in any order. */
+#ifndef PV_STATUS_
+#define PV_STATUS_
 typedef void *pv_stream_t; /* hipStream_t */
 
 #define PV_OK 0

@@ -32,12 +32,17 @@
 extern "C" {
 #endif
 
+/* The stream type and the return codes: the same block under the same guard in every public header
+ * of this project, so they can be included together in any order. */
+#ifndef PV_STATUS_
+#define PV_STATUS_
 typedef void *pv_stream_t; /* hipStream_t */
 
 #define PV_OK 0
 #define PV_EINVAL (-1)     /* bad size / pointer / enum */
 #define PV_EWORKSPACE (-2) /* workspace missing or too small */
 #define PV_EALIGN (-3)     /* pointer not aligned as documented */
+#endif
 
 /* mask / segmentation encodings accepted by the pipelines */
 #define PV_MASK_I64 0      /* int64 [b,H,W]; v3: (uint8)m != 0 (RV:533 .byte()); EVD: m == 1 (RV:340) */

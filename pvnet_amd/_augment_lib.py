@@ -2,20 +2,19 @@
 the draw of one affine map and one colour jitter per image, and the warp + background + photometric
 chain + normalisation of a u8 batch.
 
-As with ``_lib``, ``_eval_lib``, ``_pose_lib``, ``_render_lib``, ``_model_lib`` and ``_loss_lib``: no CPU
-fallback.  If the library is missing, or the tensors are not on a ROCm device, calls raise.
-``python -m pvnet_amd.build`` (or ``__graft_entry__.build()``) builds it next to libpvvote.so.
+No CPU fallback: if the library is missing, or the tensors are not on a ROCm device, calls raise
+(``_cdll`` loads it; ``python -m pvnet_amd.build`` builds it).
 """
 from __future__ import annotations
 
 import ctypes
 import os
-import threading
+
+from ._cdll import PV_EALIGN, PV_EINVAL, PV_EWORKSPACE, checker, loader  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PVAUGMENT_LIB", os.path.join(HERE, "libpvaugment.so"))
 
-PV_EINVAL, PV_EWORKSPACE, PV_EALIGN = -1, -2, -3
 PV_AUG_LABEL_I64, PV_AUG_LABEL_U8, PV_AUG_LABEL_I32 = 0, 1, 2
 PV_AUG_F32, PV_AUG_F16 = 0, 1
 PV_AUG_BRIGHTNESS, PV_AUG_CONTRAST, PV_AUG_SATURATION, PV_AUG_HUE = 1, 2, 4, 8
@@ -57,36 +56,11 @@ SIGNATURES = [
     ("pv_augment_apply", ctypes.c_int, [ctypes.POINTER(AugDesc), c_vp, ctypes.c_size_t, c_vp]),
 ]
 
-_lib = None
-_lock = threading.Lock()
-
-
-def load():
-    """Load libpvaugment.so once (raises if it is absent: no fallback path)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    with _lock:
-        if _lib is None:
-            if not os.path.exists(LIB_PATH):
-                raise RuntimeError(f"libpvaugment.so not found at {LIB_PATH}; build it with `python -m pvnet_amd.build`")
-            L = ctypes.CDLL(LIB_PATH)
-            for name, res, args in SIGNATURES:
-                fn = getattr(L, name)
-                fn.restype = res
-                fn.argtypes = args
-            _lib = L
-    return _lib
+load = loader(LIB_PATH, SIGNATURES)
 
 
 class PVAugmentError(RuntimeError):
     pass
 
 
-_ERR = {PV_EINVAL: "invalid argument", PV_EWORKSPACE: "workspace missing or too small",
-        PV_EALIGN: "pointer not aligned as documented"}
-
-
-def check(code: int, what: str):
-    if code != 0:
-        raise PVAugmentError(f"{what} failed: {_ERR.get(code, 'HIP error')} (code {code})")
+check = checker(PVAugmentError)

@@ -1,19 +1,18 @@
 """ctypes binding of libpveval.so (include/pveval.h): batched pose evaluation.
 
-As with ``_lib``: no CPU fallback.  If the library is missing, or the tensors
-are not on a ROCm device, calls raise.  ``python -m pvnet_amd.build`` (or
-``__graft_entry__.build()``) builds it next to libpvvote.so.
+No CPU fallback: if the library is missing, or the tensors are not on a ROCm device, calls raise
+(``_cdll`` loads it; ``python -m pvnet_amd.build`` builds it).
 """
 from __future__ import annotations
 
 import ctypes
 import os
-import threading
+
+from ._cdll import PV_EALIGN, PV_EINVAL, PV_EWORKSPACE, checker, loader  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PVEVAL_LIB", os.path.join(HERE, "libpveval.so"))
 
-PV_EINVAL, PV_EWORKSPACE, PV_EALIGN = -1, -2, -3
 PV_EVAL_ADD, PV_EVAL_ADDS, PV_EVAL_PROJ, PV_EVAL_PROJ_SYM, PV_EVAL_CMDEG = 1, 2, 4, 8, 16
 PV_EVAL_ALL = 31
 # metric name -> (request bit, columns of out [b][PV_EVAL_NCOL] it fills)
@@ -38,36 +37,11 @@ SIGNATURES = [
     ("pv_pose_metrics", ctypes.c_int, [ctypes.POINTER(EvalBatch), c_vp, c_vp, c_size, c_vp]),
 ]
 
-_lib = None
-_lock = threading.Lock()
-
-
-def load():
-    """Load libpveval.so once (raises if it is absent: no fallback path)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    with _lock:
-        if _lib is None:
-            if not os.path.exists(LIB_PATH):
-                raise RuntimeError(f"libpveval.so not found at {LIB_PATH}; build it with `python -m pvnet_amd.build`")
-            L = ctypes.CDLL(LIB_PATH)
-            for name, res, args in SIGNATURES:
-                fn = getattr(L, name)
-                fn.restype = res
-                fn.argtypes = args
-            _lib = L
-    return _lib
+load = loader(LIB_PATH, SIGNATURES)
 
 
 class PVEvalError(RuntimeError):
     pass
 
 
-_ERR = {PV_EINVAL: "invalid argument", PV_EWORKSPACE: "workspace missing or too small",
-        PV_EALIGN: "pointer not aligned as documented"}
-
-
-def check(code: int, what: str):
-    if code != 0:
-        raise PVEvalError(f"{what} failed: {_ERR.get(code, 'HIP error')} (code {code})")
+check = checker(PVEvalError)

@@ -8,7 +8,8 @@ from __future__ import annotations
 
 import ctypes
 import os
-import threading
+
+from ._cdll import loader
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PVVOTE_LIB", os.path.join(HERE, "libpvvote.so"))
@@ -108,26 +109,7 @@ SIGNATURES = [
     ("pv_upsample2x_cat_f32", ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
 ]
 
-_lib = None
-_lock = threading.Lock()
-
-
-def load():
-    """Load libpvvote.so once (raises if it is absent: no fallback path)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    with _lock:
-        if _lib is None:
-            if not os.path.exists(LIB_PATH):
-                raise RuntimeError(f"libpvvote.so not found at {LIB_PATH}; build it with `python -m pvnet_amd.build`")
-            L = ctypes.CDLL(LIB_PATH)
-            for name, res, args in SIGNATURES:
-                fn = getattr(L, name)
-                fn.restype = res
-                fn.argtypes = args
-            _lib = L
-    return _lib
+load = loader(LIB_PATH, SIGNATURES)
 
 
 class PVError(RuntimeError):

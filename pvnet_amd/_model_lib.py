@@ -1,20 +1,19 @@
 """ctypes binding of libpvmodel.so (include/pvmodel.h): the bounding box, centroid, farthest-point
 keypoints and diameter of every model of a table.
 
-As with ``_lib``, ``_eval_lib``, ``_pose_lib`` and ``_render_lib``: no CPU fallback.  If the library is
-missing, or the tensors are not on a ROCm device, calls raise.  ``python -m pvnet_amd.build`` (or
-``__graft_entry__.build()``) builds it next to libpvvote.so.
+No CPU fallback: if the library is missing, or the tensors are not on a ROCm device, calls raise
+(``_cdll`` loads it; ``python -m pvnet_amd.build`` builds it).
 """
 from __future__ import annotations
 
 import ctypes
 import os
-import threading
+
+from ._cdll import PV_EALIGN, PV_EINVAL, PV_EWORKSPACE, checker, loader  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PVMODEL_LIB", os.path.join(HERE, "libpvmodel.so"))
 
-PV_EINVAL, PV_EWORKSPACE, PV_EALIGN = -1, -2, -3
 PV_MODEL_SUM_LANES = 256
 PV_MODEL_MAX_K = 1024
 PV_MODEL_BLOCK_MAX_PN = 12288
@@ -39,36 +38,11 @@ SIGNATURES = [
     ("pv_model_diameter", ctypes.c_int, [ctypes.POINTER(ModelPoints), c_vp, c_vp, ctypes.c_size_t, c_vp]),
 ]
 
-_lib = None
-_lock = threading.Lock()
-
-
-def load():
-    """Load libpvmodel.so once (raises if it is absent: no fallback path)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    with _lock:
-        if _lib is None:
-            if not os.path.exists(LIB_PATH):
-                raise RuntimeError(f"libpvmodel.so not found at {LIB_PATH}; build it with `python -m pvnet_amd.build`")
-            L = ctypes.CDLL(LIB_PATH)
-            for name, res, args in SIGNATURES:
-                fn = getattr(L, name)
-                fn.restype = res
-                fn.argtypes = args
-            _lib = L
-    return _lib
+load = loader(LIB_PATH, SIGNATURES)
 
 
 class PVModelError(RuntimeError):
     pass
 
 
-_ERR = {PV_EINVAL: "invalid argument", PV_EWORKSPACE: "workspace missing or too small",
-        PV_EALIGN: "pointer not aligned as documented"}
-
-
-def check(code: int, what: str):
-    if code != 0:
-        raise PVModelError(f"{what} failed: {_ERR.get(code, 'HIP error')} (code {code})")
+check = checker(PVModelError)

@@ -1,20 +1,19 @@
 """ctypes binding of libpvrender.so (include/pvrender.h): label / instance / depth maps from
 meshes and poses, and the unit vector field from a label map and keypoints.
 
-As with ``_lib``, ``_eval_lib`` and ``_pose_lib``: no CPU fallback.  If the library is missing, or
-the tensors are not on a ROCm device, calls raise.  ``python -m pvnet_amd.build`` (or
-``__graft_entry__.build()``) builds it next to libpvvote.so.
+No CPU fallback: if the library is missing, or the tensors are not on a ROCm device, calls raise
+(``_cdll`` loads it; ``python -m pvnet_amd.build`` builds it).
 """
 from __future__ import annotations
 
 import ctypes
 import os
-import threading
+
+from ._cdll import PV_EALIGN, PV_EINVAL, PV_EWORKSPACE, checker, loader  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PVRENDER_LIB", os.path.join(HERE, "libpvrender.so"))
 
-PV_EINVAL, PV_EWORKSPACE, PV_EALIGN = -1, -2, -3
 PV_LABEL_I64, PV_LABEL_U8, PV_LABEL_I32 = 0, 1, 2
 PV_FIELD_F32, PV_FIELD_F16 = 0, 1
 PV_KP_F64, PV_KP_F32 = 0, 1
@@ -56,36 +55,11 @@ SIGNATURES = [
     ("pv_vertex_field", ctypes.c_int, [ctypes.POINTER(FieldDesc), c_vp]),
 ]
 
-_lib = None
-_lock = threading.Lock()
-
-
-def load():
-    """Load libpvrender.so once (raises if it is absent: no fallback path)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    with _lock:
-        if _lib is None:
-            if not os.path.exists(LIB_PATH):
-                raise RuntimeError(f"libpvrender.so not found at {LIB_PATH}; build it with `python -m pvnet_amd.build`")
-            L = ctypes.CDLL(LIB_PATH)
-            for name, res, args in SIGNATURES:
-                fn = getattr(L, name)
-                fn.restype = res
-                fn.argtypes = args
-            _lib = L
-    return _lib
+load = loader(LIB_PATH, SIGNATURES)
 
 
 class PVRenderError(RuntimeError):
     pass
 
 
-_ERR = {PV_EINVAL: "invalid argument", PV_EWORKSPACE: "workspace missing or too small",
-        PV_EALIGN: "pointer not aligned as documented"}
-
-
-def check(code: int, what: str):
-    if code != 0:
-        raise PVRenderError(f"{what} failed: {_ERR.get(code, 'HIP error')} (code {code})")
+check = checker(PVRenderError)

@@ -1,5 +1,4 @@
-"""Build libpvvote.so, libpveval.so, libpvpose.so, libpvrender.so, libpvmodel.so, libpvloss.so and
-libpvaugment.so (the HIP C-ABI libraries) in-tree for gfx950.
+"""Build the HIP C-ABI libraries (the table LIBS) in-tree for gfx950.
 
     python -m pvnet_amd.build            # or __graft_entry__.build()
 
@@ -9,54 +8,48 @@ travel to the GPU box with the repository snapshot.
 from __future__ import annotations
 
 import os
+import re
 import shutil
 import subprocess
 import sys
+from typing import NamedTuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
-# the translation units (csrc/pvvote.hip's head comment maps the vote library's)
-SRCS = [os.path.join(CSRC, n) for n in (
-    "pvvote.hip", "pvapi.hip", "pvpipeline.hip", "pvcompact.hip", "pvrefine.hip", "pvevd.hip", "pvpnp.hip",
-    "pvdecoder.hip", "pvconv.hip")]
-HDR = os.path.join(REPO, "include", "pvvote.h")
-OUT = os.path.join(HERE, "libpvvote.so")
-# the pose-evaluation library (include/pveval.h): a library of its own, so libpvvote.so's
-# export list and translation-unit count hold still
-EVAL_SRCS = [os.path.join(CSRC, "pveval.hip")]
-EVAL_HDR = os.path.join(REPO, "include", "pveval.h")
-EVAL_OUT = os.path.join(HERE, "libpveval.so")
-# the plain-PnP library (include/pvpose.h), a third library for the same reason; pvepnp_core.h is
-# its kernel's body and belongs to it alone
-POSE_SRCS = [os.path.join(CSRC, "pvepnp.hip")]
-POSE_HDR = os.path.join(REPO, "include", "pvpose.h")
-POSE_OUT = os.path.join(HERE, "libpvpose.so")
-POSE_DEPS = (*POSE_SRCS, os.path.join(CSRC, "pvepnp_core.h"), POSE_HDR)
-# the render library (include/pvrender.h), a fourth for the same reason; its one translation unit
-# includes no other file of csrc/
-RENDER_SRCS = [os.path.join(CSRC, "pvrender.hip")]
-RENDER_HDR = os.path.join(REPO, "include", "pvrender.h")
-RENDER_OUT = os.path.join(HERE, "libpvrender.so")
-RENDER_DEPS = (*RENDER_SRCS, RENDER_HDR)
-# the model-preparation library (include/pvmodel.h), a fifth; like the render library its one
-# translation unit includes no other file of csrc/
-MODEL_SRCS = [os.path.join(CSRC, "pvmodel.hip")]
-MODEL_HDR = os.path.join(REPO, "include", "pvmodel.h")
-MODEL_OUT = os.path.join(HERE, "libpvmodel.so")
-MODEL_DEPS = (*MODEL_SRCS, MODEL_HDR)
-# the training-loss library (include/pvloss.h), a sixth; again one translation unit that includes no
-# other file of csrc/
-LOSS_SRCS = [os.path.join(CSRC, "pvloss.hip")]
-LOSS_HDR = os.path.join(REPO, "include", "pvloss.h")
-LOSS_OUT = os.path.join(HERE, "libpvloss.so")
-LOSS_DEPS = (*LOSS_SRCS, LOSS_HDR)
-# the training-augmentation library (include/pvaugment.h), a seventh; one translation unit that
-# includes no other file of csrc/
-AUG_SRCS = [os.path.join(CSRC, "pvaugment.hip")]
-AUG_HDR = os.path.join(REPO, "include", "pvaugment.h")
-AUG_OUT = os.path.join(HERE, "libpvaugment.so")
-AUG_DEPS = (*AUG_SRCS, AUG_HDR)
+
+
+class Lib(NamedTuple):
+    out: str    # the shared library, next to this file
+    hdr: str    # its public header under include/
+    srcs: list  # its translation units under csrc/
+
+
+def _lib(name: str, *srcs: str) -> Lib:
+    return Lib(os.path.join(HERE, f"lib{name}.so"), os.path.join(REPO, "include", name + ".h"),
+               [os.path.join(CSRC, s) for s in srcs])
+
+
+# Every library, in build order: one row here, one loader module, one public header and its own
+# tests make a library.  What a library depends on is not listed: closure() reads it from the sources.
+LIBS = {
+    # the translation units (csrc/pvvote.hip's head comment maps the vote library's)
+    "vote": _lib("pvvote", "pvvote.hip", "pvapi.hip", "pvpipeline.hip", "pvcompact.hip", "pvrefine.hip", "pvevd.hip",
+                 "pvpnp.hip", "pvdecoder.hip", "pvconv.hip"),
+    # the pose-evaluation library (include/pveval.h): a library of its own, so libpvvote.so's
+    # export list and translation-unit count hold still; so is each library below
+    "eval": _lib("pveval", "pveval.hip"),
+    # the plain-PnP library (include/pvpose.h); pvepnp_core.h is its kernel's body and belongs to
+    # it alone
+    "pose": _lib("pvpose", "pvepnp.hip"),
+    # the render (include/pvrender.h), model-preparation (include/pvmodel.h), training-loss
+    # (include/pvloss.h) and training-augmentation (include/pvaugment.h) libraries: one translation
+    # unit each, which includes no other file of csrc/
+    "render": _lib("pvrender", "pvrender.hip"),
+    "model": _lib("pvmodel", "pvmodel.hip"),
+    "loss": _lib("pvloss", "pvloss.hip"),
+    "augment": _lib("pvaugment", "pvaugment.hip"),
+}
 ARCH = os.environ.get("PVVOTE_ARCH", "gfx950")
 
 HIPCC_FLAGS = [
@@ -87,27 +80,41 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found (ROCm install required to build libpvvote.so)")
 
 
-def stale(out: str) -> bool:
-    """Is `out` missing, or older than any source under csrc/, a public header or this file?
-    For each library the other six's translation units and public headers do not count, and
-    libpvrender.so, libpvmodel.so, libpvloss.so and libpvaugment.so, which include nothing else of
-    csrc/, depend on their own sources alone."""
-    if not os.path.exists(out):
+_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.M)
+
+
+def closure(srcs) -> list:
+    """`srcs` and every file they reach through #include "...", resolved relative to the including
+    file and normalised, so one file is one string however it was reached.  <...> includes (the
+    toolchain's) are not followed."""
+    seen = [os.path.normpath(s) for s in srcs]
+    for path in seen:               # grows while it is walked
+        with open(path) as f:
+            for inc in _INCLUDE.findall(f.read()):
+                dep = os.path.normpath(os.path.join(os.path.dirname(path), inc))
+                if dep not in seen:
+                    seen.append(dep)
+    return seen
+
+
+def older(path: str, deps) -> bool:
+    """Is `path` missing, or older than any of `deps`?"""
+    if not os.path.exists(path):
         return True
-    t = os.path.getmtime(out)
-    own = {RENDER_OUT: RENDER_DEPS, MODEL_OUT: MODEL_DEPS, LOSS_OUT: LOSS_DEPS, AUG_OUT: AUG_DEPS}.get(out)
-    if own is not None:
-        return any(os.path.getmtime(p) > t for p in (*own, __file__))
-    other = {OUT: (*EVAL_SRCS, EVAL_HDR, *POSE_DEPS, *RENDER_DEPS, *MODEL_DEPS, *LOSS_DEPS, *AUG_DEPS),
-             EVAL_OUT: (*SRCS, *POSE_DEPS, *RENDER_DEPS, *MODEL_DEPS, *LOSS_DEPS, *AUG_DEPS),
-             POSE_OUT: (*SRCS, *EVAL_SRCS, EVAL_HDR, *RENDER_DEPS, *MODEL_DEPS, *LOSS_DEPS, *AUG_DEPS)}.get(out, ())
-    deps = [os.path.join(CSRC, n) for n in os.listdir(CSRC) if n.endswith((".hip", ".h"))]
-    return any(os.path.getmtime(p) > t for p in (*deps, HDR, EVAL_HDR, POSE_HDR, RENDER_HDR, __file__)
-               if p not in other)
+    t = os.path.getmtime(path)
+    return any(os.path.getmtime(p) > t for p in deps)
+
+
+def stale(out: str) -> bool:
+    """Is the library `out` missing, or older than a file the compiler reads for it or this file?"""
+    srcs = {lib.out: lib.srcs for lib in LIBS.values()}
+    if out not in srcs:
+        raise ValueError(f"{out} is not a library of LIBS; for another file use older(path, deps)")
+    return older(out, (*closure(srcs[out]), __file__))
 
 
 def needs_build() -> bool:
-    return any(stale(o) for o in (OUT, EVAL_OUT, POSE_OUT, RENDER_OUT, MODEL_OUT, LOSS_OUT, AUG_OUT))
+    return any(stale(lib.out) for lib in LIBS.values())
 
 
 def _link(out: str, srcs, extra=()) -> None:
@@ -120,23 +127,11 @@ def _link(out: str, srcs, extra=()) -> None:
 
 
 def build(force: bool = False, extra=()) -> str:
-    """Build libpvvote.so, libpveval.so, libpvpose.so, libpvrender.so, libpvmodel.so, libpvloss.so and
-    libpvaugment.so (each when stale); returns libpvvote.so's path."""
-    if force or stale(OUT):
-        _link(OUT, SRCS, extra)
-    if force or stale(EVAL_OUT):
-        _link(EVAL_OUT, EVAL_SRCS, extra)
-    if force or stale(POSE_OUT):
-        _link(POSE_OUT, POSE_SRCS, extra)
-    if force or stale(RENDER_OUT):
-        _link(RENDER_OUT, RENDER_SRCS, extra)
-    if force or stale(MODEL_OUT):
-        _link(MODEL_OUT, MODEL_SRCS, extra)
-    if force or stale(LOSS_OUT):
-        _link(LOSS_OUT, LOSS_SRCS, extra)
-    if force or stale(AUG_OUT):
-        _link(AUG_OUT, AUG_SRCS, extra)
-    return OUT
+    """Build every library of LIBS (each when stale); returns libpvvote.so's path."""
+    for lib in LIBS.values():
+        if force or stale(lib.out):
+            _link(lib.out, lib.srcs, extra)
+    return LIBS["vote"].out
 
 
 def asm(tu: str = "pvvote.hip", path: str | None = None, extra=()) -> str:

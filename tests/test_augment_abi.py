@@ -1,12 +1,12 @@
 """CPU-side checks of libpvaugment.so (include/pvaugment.h): it builds for gfx950, exports exactly its
-header, rejects bad arguments on the host, and leaves the other six libraries as they were."""
+header, and rejects bad arguments on the host."""
 import ctypes
 import os
 import re
 
 import pytest
 
-from tests.test_render_abi import exported, header_functions
+from tests.test_build_table import exported, header_functions
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["pv_augment_apply", "pv_augment_params", "pv_augment_workspace_size", "pv_label_stats"]
@@ -21,21 +21,22 @@ def lib():
 
 def test_library_builds_for_gfx950(lib):
     from pvnet_amd import build
-    assert build.AUG_OUT == os.path.join(REPO, "pvnet_amd", "libpvaugment.so")
-    assert build.AUG_HDR == os.path.join(REPO, "include", "pvaugment.h")
-    assert [os.path.basename(s) for s in build.AUG_SRCS] == ["pvaugment.hip"]
-    assert set(build.AUG_DEPS) == {*build.AUG_SRCS, build.AUG_HDR}
-    assert b"gfx950" in open(build.AUG_OUT, "rb").read()
-    assert build.build() == build.OUT and not build.needs_build()
+    aug = build.LIBS["augment"]
+    assert aug.out == os.path.join(REPO, "pvnet_amd", "libpvaugment.so")
+    assert aug.hdr == os.path.join(REPO, "include", "pvaugment.h")
+    assert [os.path.basename(s) for s in aug.srcs] == ["pvaugment.hip"]
+    assert set(build.closure(aug.srcs)) == {*aug.srcs, aug.hdr}
+    assert b"gfx950" in open(aug.out, "rb").read()
+    assert build.build() == build.LIBS["vote"].out and not build.needs_build()
     # the translation unit includes nothing else of csrc/, no floating-point atomic, no fast-math form
-    src = open(build.AUG_SRCS[0]).read()
+    src = open(aug.srcs[0]).read()
     assert [i for i in re.findall(r'#include "([^"]+)"', src)] == ["../../include/pvaugment.h"]
     assert "-ffp-contract=off" in build.HIPCC_FLAGS
     assert not re.search(r"__expf|__fdividef|__sinf|__cosf|atomicAdd\(\s*\(?(float|double)", src)
     # per-pixel trigonometry has no place in the sampler: cos and sin appear in k_params alone
     assert len(re.findall(r"\b(?:cos|sin)f?\(", src)) == 2
     # the reference functions the header replaces are named in it, and what is out of scope
-    hdr = open(build.AUG_HDR).read()
+    hdr = open(aug.hdr).read()
     for name in ("LineModDatasetRealAug", "rotate_instance", "crop_resize_instance_v1", "crop_or_padding_to_fixed_size",
                  "ColorJitter", "compute_vertex", "NOT A REPLAY", "blur", "noise", "flips", "occlusion"):
         assert name in hdr, name
@@ -44,7 +45,7 @@ def test_library_builds_for_gfx950(lib):
 def test_exports_exactly_the_header(lib):
     from pvnet_amd import build, _augment_lib
     assert header_functions("pvaugment.h") == NAMES
-    assert exported(build.AUG_OUT) == set(NAMES)
+    assert exported(build.LIBS["augment"].out) == set(NAMES)
     assert {n for n, _, _ in _augment_lib.SIGNATURES} == set(NAMES)
     for n in NAMES:
         assert hasattr(lib, n), f"{n} has no ctypes signature in pvnet_amd/_augment_lib.py"
@@ -69,9 +70,6 @@ def test_header_constants_match_binding():
     assert defs["PV_AUG_MAX_DIM"] == P.PV_AUG_MAX_DIM == 2 ** 20
     assert defs["PV_AUG_MAX_CLASSES"] == P.PV_AUG_MAX_CLASSES == 1024
     assert defs["PV_AUG_DRAWS"] == P.PV_AUG_DRAWS == 8
-    # the guard knows the other six headers
-    for g in ("PVVOTE_H_", "PVEVAL_H_", "PVPOSE_H_", "PVRENDER_H_", "PVMODEL_H_", "PVLOSS_H_"):
-        assert f"!defined({g})" in src
     # the generator's constants are the header's, and the numpy restatement's
     from tests import augment_ref as R
     for c in ("0xBF58476D1CE4E5B9", "0x94D049BB133111EB", "0x9E3779B97F4A7C15"):
@@ -224,48 +222,6 @@ def test_argument_errors_without_device(lib):
     assert apply(desc(b=0, image=None, label=None, inv=None, color=None, background=None, out_image=None, out_label=None),
                  ws=None, nbytes=0) == 0
     assert apply(desc(b=0, flags=99)) == P.PV_EINVAL and apply(desc(b=0, std=(0, 1, 1))) == P.PV_EINVAL
-
-
-def test_other_libraries_are_undisturbed(lib, monkeypatch):
-    """The seven-library staleness matrix: an edit to the augmentation sources makes only libpvaugment.so
-    stale, an edit to the others' sources or shared headers does not touch it; the other six export what
-    their own pinned tests expect."""
-    from pvnet_amd import build
-    from tests.test_abi import OTHER_EXPORTS, PV_EXPORTS
-    assert exported(build.OUT) == set(PV_EXPORTS) | OTHER_EXPORTS
-    assert exported(build.EVAL_OUT) == {"pv_eval_workspace_size", "pv_nearest_point_idx", "pv_pose_metrics"}
-    assert exported(build.POSE_OUT) == {"pv_epnp", "pv_rt6_to_Rt"}
-    assert exported(build.RENDER_OUT) == {"pv_render_labels", "pv_render_workspace_size", "pv_vertex_field"}
-    assert exported(build.MODEL_OUT) == {"pv_farthest_points", "pv_model_diameter", "pv_model_extent", "pv_model_workspace_size"}
-    assert exported(build.LOSS_OUT) == {"pv_loss_backward", "pv_loss_forward", "pv_loss_workspace_size"}
-    others = set(build.SRCS) | set(build.EVAL_SRCS) | set(build.POSE_DEPS) | set(build.RENDER_DEPS) | \
-        set(build.MODEL_DEPS) | set(build.LOSS_DEPS) | {build.HDR, build.EVAL_HDR}
-    assert not set(build.AUG_DEPS) & others
-    outs = (build.OUT, build.EVAL_OUT, build.POSE_OUT, build.RENDER_OUT, build.MODEL_OUT, build.LOSS_OUT, build.AUG_OUT)
-    # an edit is simulated by the modification times stale() sees; no file is touched
-    real = os.path.getmtime
-    newest = max(real(p) for p in outs) + 10
-
-    def stale_after(paths):
-        monkeypatch.setattr(build.os.path, "getmtime", lambda p: newest if p in paths else real(p))
-        return tuple(build.stale(o) for o in outs)
-
-    F, T = False, True
-    assert stale_after(set(build.AUG_DEPS)) == (F, F, F, F, F, F, T)
-    assert stale_after({build.AUG_HDR}) == (F, F, F, F, F, F, T)
-    assert stale_after(set(build.AUG_SRCS)) == (F, F, F, F, F, F, T)
-    assert stale_after(others) == (T, T, T, T, T, T, F)
-    assert stale_after(set(build.LOSS_DEPS)) == (F, F, F, F, F, T, F)
-    assert stale_after(set(build.MODEL_DEPS)) == (F, F, F, F, T, F, F)
-    assert stale_after(set(build.RENDER_DEPS)) == (F, F, F, T, F, F, F)
-    assert stale_after(set(build.POSE_DEPS)) == (F, F, T, F, F, F, F)
-    assert stale_after({*build.EVAL_SRCS, build.EVAL_HDR}) == (F, T, F, F, F, F, F)
-    assert stale_after(set(build.SRCS)) == (T, F, F, F, F, F, F)
-    shared = {os.path.join(build.CSRC, "pv_common.h"), os.path.join(build.CSRC, "pv_host.h")}
-    assert stale_after(shared)[3:] == (F, F, F, F)
-    assert stale_after({build.__file__}) == (T, T, T, T, T, T, T)
-    monkeypatch.undo()
-    assert not build.needs_build()
 
 
 def test_python_layer_rejects_before_any_call():

@@ -142,9 +142,9 @@ def lib():
 
 def test_library_builds_for_gfx950(lib):
     from pvnet_amd import build
-    assert build.EVAL_OUT == os.path.join(REPO, "pvnet_amd", "libpveval.so")
-    assert b"gfx950" in open(build.EVAL_OUT, "rb").read()
-    assert build.build() == build.OUT and not build.needs_build()
+    assert build.LIBS["eval"].out == os.path.join(REPO, "pvnet_amd", "libpveval.so")
+    assert b"gfx950" in open(build.LIBS["eval"].out, "rb").read()
+    assert build.build() == build.LIBS["vote"].out and not build.needs_build()
 
 
 def test_header_symbols_exported(lib):
@@ -159,7 +159,7 @@ def test_header_symbols_exported(lib):
 
 def test_exports_only_the_abi(lib):
     from pvnet_amd import build
-    out = subprocess.run(["nm", "-D", "--defined-only", build.EVAL_OUT], capture_output=True, text=True,
+    out = subprocess.run(["nm", "-D", "--defined-only", build.LIBS["eval"].out], capture_output=True, text=True,
                          check=True).stdout
     names = {line.split()[-1] for line in out.splitlines() if line.strip()}
     names = {n for n in names if not re.fullmatch(r"__hip_cuid_[0-9a-f]+", n)}

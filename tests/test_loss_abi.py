@@ -1,12 +1,12 @@
 """CPU-side checks of libpvloss.so (include/pvloss.h): it builds for gfx950, exports exactly its
-header, rejects bad arguments on the host, and leaves the other five libraries as they were."""
+header, and rejects bad arguments on the host."""
 import ctypes
 import os
 import re
 
 import pytest
 
-from tests.test_render_abi import exported, header_functions
+from tests.test_build_table import exported, header_functions
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["pv_loss_backward", "pv_loss_forward", "pv_loss_workspace_size"]
@@ -21,19 +21,20 @@ def lib():
 
 def test_library_builds_for_gfx950(lib):
     from pvnet_amd import build
-    assert build.LOSS_OUT == os.path.join(REPO, "pvnet_amd", "libpvloss.so")
-    assert build.LOSS_HDR == os.path.join(REPO, "include", "pvloss.h")
-    assert [os.path.basename(s) for s in build.LOSS_SRCS] == ["pvloss.hip"]
-    assert set(build.LOSS_DEPS) == {*build.LOSS_SRCS, build.LOSS_HDR}
-    assert b"gfx950" in open(build.LOSS_OUT, "rb").read()
-    assert build.build() == build.OUT and not build.needs_build()
+    loss = build.LIBS["loss"]
+    assert loss.out == os.path.join(REPO, "pvnet_amd", "libpvloss.so")
+    assert loss.hdr == os.path.join(REPO, "include", "pvloss.h")
+    assert [os.path.basename(s) for s in loss.srcs] == ["pvloss.hip"]
+    assert set(build.closure(loss.srcs)) == {*loss.srcs, loss.hdr}
+    assert b"gfx950" in open(loss.out, "rb").read()
+    assert build.build() == build.LIBS["vote"].out and not build.needs_build()
     # the translation unit includes nothing else of csrc/, and no floating-point atomic
-    src = open(build.LOSS_SRCS[0]).read()
+    src = open(loss.srcs[0]).read()
     assert [i for i in re.findall(r'#include "([^"]+)"', src)] == ["../../include/pvloss.h"]
     assert "-ffp-contract=off" in build.HIPCC_FLAGS
     assert not re.search(r"__expf|__logf|__fdividef|atomicAdd\(\s*\(?(float|double)", src)
     # the reference functions the header replaces are named in it
-    hdr = open(build.LOSS_HDR).read()
+    hdr = open(loss.hdr).read()
     for name in ("smooth_l1_loss", "compute_precision_recall", "CrossEntropyLoss", "net_utils.py", "train_linemod.py"):
         assert name in hdr, name
 
@@ -41,7 +42,7 @@ def test_library_builds_for_gfx950(lib):
 def test_exports_exactly_the_header(lib):
     from pvnet_amd import build, _loss_lib
     assert header_functions("pvloss.h") == NAMES
-    assert exported(build.LOSS_OUT) == set(NAMES)
+    assert exported(build.LIBS["loss"].out) == set(NAMES)
     assert {n for n, _, _ in _loss_lib.SIGNATURES} == set(NAMES)
     for n in NAMES:
         assert hasattr(lib, n), f"{n} has no ctypes signature in pvnet_amd/_loss_lib.py"
@@ -65,9 +66,6 @@ def test_header_constants_match_binding():
     assert defs["PV_LOSS_MAX_CHUNKS"] == P.PV_LOSS_MAX_CHUNKS == 8
     # a forward block's LDS (the f64 tree and 12 bytes a class) stays far below a CU's 160 KiB
     assert P.PV_LOSS_THREADS * 8 + 12 * P.PV_LOSS_MAX_CLASSES <= 64 * 1024
-    # the guard knows the other five headers
-    for g in ("PVVOTE_H_", "PVEVAL_H_", "PVPOSE_H_", "PVRENDER_H_", "PVMODEL_H_"):
-        assert f"!defined({g})" in src
     # the structures are the header's
     assert ctypes.sizeof(P.LossDesc) == 4 * 8 + 17 * 8 + 9 * 4 + 4 == 208
     assert P.LossDesc.seg_strides.offset == 32 and P.LossDesc.vertex_strides.offset == 64
@@ -193,46 +191,6 @@ def test_argument_errors_without_device(lib):
     assert bwd(desc(b=0, seg=None, vertex=None, target=None, label=None),
                grads(g_seg=None, g_vertex=None, fg=None, grad_seg=None, grad_vertex=None)) == 0
     assert both(desc(b=0, vn=0)) == P.PV_EINVAL and both(desc(b=0, sigma=0.0)) == P.PV_EINVAL
-
-
-def test_other_libraries_are_undisturbed(lib, monkeypatch):
-    """The six-library staleness matrix: an edit to the loss sources makes only libpvloss.so stale, an
-    edit to the others' sources or shared headers does not touch it; the other five export what their
-    own pinned tests expect."""
-    from pvnet_amd import build
-    from tests.test_abi import OTHER_EXPORTS, PV_EXPORTS
-    assert exported(build.OUT) == set(PV_EXPORTS) | OTHER_EXPORTS
-    assert exported(build.EVAL_OUT) == {"pv_eval_workspace_size", "pv_nearest_point_idx", "pv_pose_metrics"}
-    assert exported(build.POSE_OUT) == {"pv_epnp", "pv_rt6_to_Rt"}
-    assert exported(build.RENDER_OUT) == {"pv_render_labels", "pv_render_workspace_size", "pv_vertex_field"}
-    assert exported(build.MODEL_OUT) == {"pv_farthest_points", "pv_model_diameter", "pv_model_extent", "pv_model_workspace_size"}
-    others = set(build.SRCS) | set(build.EVAL_SRCS) | set(build.POSE_DEPS) | set(build.RENDER_DEPS) | \
-        set(build.MODEL_DEPS) | {build.HDR, build.EVAL_HDR}
-    assert not set(build.LOSS_DEPS) & others
-    outs = (build.OUT, build.EVAL_OUT, build.POSE_OUT, build.RENDER_OUT, build.MODEL_OUT, build.LOSS_OUT)
-    # an edit is simulated by the modification times stale() sees; no file is touched
-    real = os.path.getmtime
-    newest = max(real(p) for p in outs) + 10
-
-    def stale_after(paths):
-        monkeypatch.setattr(build.os.path, "getmtime", lambda p: newest if p in paths else real(p))
-        return tuple(build.stale(o) for o in outs)
-
-    F, T = False, True
-    assert stale_after(set(build.LOSS_DEPS)) == (F, F, F, F, F, T)
-    assert stale_after({build.LOSS_HDR}) == (F, F, F, F, F, T)
-    assert stale_after(set(build.LOSS_SRCS)) == (F, F, F, F, F, T)
-    assert stale_after(others) == (T, T, T, T, T, F)
-    assert stale_after(set(build.MODEL_DEPS)) == (F, F, F, F, T, F)
-    assert stale_after(set(build.RENDER_DEPS)) == (F, F, F, T, F, F)
-    assert stale_after(set(build.POSE_DEPS)) == (F, F, T, F, F, F)
-    assert stale_after({*build.EVAL_SRCS, build.EVAL_HDR}) == (F, T, F, F, F, F)
-    assert stale_after(set(build.SRCS)) == (T, F, F, F, F, F)
-    shared = {os.path.join(build.CSRC, "pv_common.h"), os.path.join(build.CSRC, "pv_host.h")}
-    assert stale_after(shared)[3:] == (F, F, F)
-    assert stale_after({build.__file__}) == (T, T, T, T, T, T)
-    monkeypatch.undo()
-    assert not build.needs_build()
 
 
 def test_python_layer_rejects_before_any_call():

@@ -1,5 +1,5 @@
 """CPU-side checks of libpvmodel.so (include/pvmodel.h): it builds for gfx950, exports exactly its
-header, rejects bad arguments on the host, and leaves the other four libraries as they were."""
+header, and rejects bad arguments on the host."""
 import ctypes
 import os
 import re
@@ -7,7 +7,7 @@ import re
 import pytest
 
 from tests import model_ref as M
-from tests.test_render_abi import exported, header_functions
+from tests.test_build_table import exported, header_functions
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["pv_farthest_points", "pv_model_diameter", "pv_model_extent", "pv_model_workspace_size"]
@@ -22,14 +22,15 @@ def lib():
 
 def test_library_builds_for_gfx950(lib):
     from pvnet_amd import build
-    assert build.MODEL_OUT == os.path.join(REPO, "pvnet_amd", "libpvmodel.so")
-    assert build.MODEL_HDR == os.path.join(REPO, "include", "pvmodel.h")
-    assert [os.path.basename(s) for s in build.MODEL_SRCS] == ["pvmodel.hip"]
-    assert set(build.MODEL_DEPS) == {*build.MODEL_SRCS, build.MODEL_HDR}
-    assert b"gfx950" in open(build.MODEL_OUT, "rb").read()
-    assert build.build() == build.OUT and not build.needs_build()
+    model = build.LIBS["model"]
+    assert model.out == os.path.join(REPO, "pvnet_amd", "libpvmodel.so")
+    assert model.hdr == os.path.join(REPO, "include", "pvmodel.h")
+    assert [os.path.basename(s) for s in model.srcs] == ["pvmodel.hip"]
+    assert set(build.closure(model.srcs)) == {*model.srcs, model.hdr}
+    assert b"gfx950" in open(model.out, "rb").read()
+    assert build.build() == build.LIBS["vote"].out and not build.needs_build()
     # the translation unit includes nothing else of csrc/
-    src = open(build.MODEL_SRCS[0]).read()
+    src = open(model.srcs[0]).read()
     assert [i for i in re.findall(r'#include "([^"]+)"', src)] == ["../../include/pvmodel.h"]
     assert "-ffp-contract=off" in build.HIPCC_FLAGS
 
@@ -37,7 +38,7 @@ def test_library_builds_for_gfx950(lib):
 def test_exports_exactly_the_header(lib):
     from pvnet_amd import build, _model_lib
     assert header_functions("pvmodel.h") == NAMES
-    assert exported(build.MODEL_OUT) == set(NAMES)
+    assert exported(build.LIBS["model"].out) == set(NAMES)
     assert {n for n, _, _ in _model_lib.SIGNATURES} == set(NAMES)
     for n in NAMES:
         assert hasattr(lib, n), f"{n} has no ctypes signature in pvnet_amd/_model_lib.py"
@@ -127,43 +128,6 @@ def test_argument_errors_without_device(lib):
     assert ext(points(points=None, off=None, **empty), bbox=None, cen=None, cnt=None) == 0
     assert dia(points(points=None, off=None, **empty), out=None, ws=None, nbytes=0) == 0
     assert fps(points(**empty), k=0) == P.PV_EINVAL and fps(points(**empty), start=7) == P.PV_EINVAL
-
-
-def test_other_libraries_are_undisturbed(lib, monkeypatch):
-    """The five-library staleness matrix: an edit to the model sources makes only libpvmodel.so
-    stale, an edit to the others' sources or shared headers does not touch it; the other four export
-    what their own pinned tests expect."""
-    from pvnet_amd import build
-    from tests.test_abi import OTHER_EXPORTS, PV_EXPORTS
-    assert exported(build.OUT) == set(PV_EXPORTS) | OTHER_EXPORTS
-    assert exported(build.EVAL_OUT) == {"pv_eval_workspace_size", "pv_nearest_point_idx", "pv_pose_metrics"}
-    assert exported(build.POSE_OUT) == {"pv_epnp", "pv_rt6_to_Rt"}
-    assert exported(build.RENDER_OUT) == {"pv_render_labels", "pv_render_workspace_size", "pv_vertex_field"}
-    others = set(build.SRCS) | set(build.EVAL_SRCS) | set(build.POSE_DEPS) | set(build.RENDER_DEPS) | \
-        {build.HDR, build.EVAL_HDR}
-    assert not set(build.MODEL_DEPS) & others
-    outs = (build.OUT, build.EVAL_OUT, build.POSE_OUT, build.RENDER_OUT, build.MODEL_OUT)
-    # an edit is simulated by the modification times stale() sees; no file is touched
-    real = os.path.getmtime
-    newest = max(real(p) for p in outs) + 10
-
-    def stale_after(paths):
-        monkeypatch.setattr(build.os.path, "getmtime", lambda p: newest if p in paths else real(p))
-        return tuple(build.stale(o) for o in outs)
-
-    assert stale_after(set(build.MODEL_DEPS)) == (False, False, False, False, True)
-    assert stale_after({build.MODEL_HDR}) == (False, False, False, False, True)
-    assert stale_after(set(build.MODEL_SRCS)) == (False, False, False, False, True)
-    assert stale_after(others) == (True, True, True, True, False)
-    assert stale_after(set(build.RENDER_DEPS)) == (False, False, False, True, False)
-    assert stale_after(set(build.POSE_DEPS)) == (False, False, True, False, False)
-    assert stale_after({*build.EVAL_SRCS, build.EVAL_HDR}) == (False, True, False, False, False)
-    assert stale_after(set(build.SRCS)) == (True, False, False, False, False)
-    shared = {os.path.join(build.CSRC, "pv_common.h"), os.path.join(build.CSRC, "pv_host.h")}
-    assert stale_after(shared)[3:] == (False, False)
-    assert stale_after({build.__file__}) == (True, True, True, True, True)
-    monkeypatch.undo()
-    assert not build.needs_build()
 
 
 def test_python_layer_rejects_before_any_call():

@@ -1,26 +1,15 @@
 """CPU-side checks of libpvpose.so (include/pvpose.h): it builds for gfx950, exports exactly its
-header, rejects bad arguments on the host, and leaves the other two libraries as they were."""
+header, and rejects bad arguments on the host."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.test_build_table import exported, header_functions
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def header_functions(name):
-    src = open(os.path.join(REPO, "include", name)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(pv_[A-Za-z0-9_]+)\s*\(", src)))
-
-
-def exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    return {n for n in names if not re.fullmatch(r"__hip_cuid_[0-9a-f]+", n)}
 
 
 @pytest.fixture(scope="module")
@@ -32,18 +21,19 @@ def lib():
 
 def test_library_builds_for_gfx950(lib):
     from pvnet_amd import build
-    assert build.POSE_OUT == os.path.join(REPO, "pvnet_amd", "libpvpose.so")
-    assert build.POSE_HDR == os.path.join(REPO, "include", "pvpose.h")
-    assert [os.path.basename(s) for s in build.POSE_SRCS] == ["pvepnp.hip"]
-    assert b"gfx950" in open(build.POSE_OUT, "rb").read()
-    assert build.build() == build.OUT and not build.needs_build()
+    pose = build.LIBS["pose"]
+    assert pose.out == os.path.join(REPO, "pvnet_amd", "libpvpose.so")
+    assert pose.hdr == os.path.join(REPO, "include", "pvpose.h")
+    assert [os.path.basename(s) for s in pose.srcs] == ["pvepnp.hip"]
+    assert b"gfx950" in open(pose.out, "rb").read()
+    assert build.build() == build.LIBS["vote"].out and not build.needs_build()
 
 
 def test_exports_exactly_the_header(lib):
     from pvnet_amd import build, _pose_lib
     names = header_functions("pvpose.h")
     assert names == ["pv_epnp", "pv_rt6_to_Rt"]
-    assert exported(build.POSE_OUT) == set(names)
+    assert exported(build.LIBS["pose"].out) == set(names)
     bound = {n for n, _, _ in _pose_lib.SIGNATURES}
     for n in names:
         assert hasattr(lib, n) and n in bound, f"{n} has no ctypes signature in pvnet_amd/_pose_lib.py"
@@ -92,29 +82,6 @@ def test_argument_errors_without_device(lib):
     assert f(p, p, -1, None) == P.PV_EINVAL
     assert f(None, p, 1, None) == P.PV_EINVAL and f(p, None, 1, None) == P.PV_EINVAL
     assert f(p, p, 0, None) == 0 and f(None, None, 0, None) == 0
-
-
-def test_other_libraries_are_undisturbed(lib, monkeypatch):
-    """libpvvote.so and libpveval.so export what their own pinned tests expect, and touching the
-    pose library's sources makes neither of them stale."""
-    from pvnet_amd import build
-    from tests.test_abi import OTHER_EXPORTS, PV_EXPORTS
-    assert exported(build.OUT) == set(PV_EXPORTS) | OTHER_EXPORTS
-    assert exported(build.EVAL_OUT) == {"pv_eval_workspace_size", "pv_nearest_point_idx", "pv_pose_metrics"}
-    assert not set(build.POSE_SRCS) & (set(build.SRCS) | set(build.EVAL_SRCS))
-    # an edit is simulated by the modification times stale() sees; no file is touched
-    real = os.path.getmtime
-    newest = max(real(p) for p in (build.OUT, build.EVAL_OUT, build.POSE_OUT)) + 10
-
-    def edited(paths):
-        monkeypatch.setattr(build.os.path, "getmtime", lambda p: newest if p in paths else real(p))
-
-    edited(set(build.POSE_DEPS))
-    assert build.stale(build.POSE_OUT) and not build.stale(build.OUT) and not build.stale(build.EVAL_OUT)
-    edited({*build.SRCS, *build.EVAL_SRCS, build.EVAL_HDR})
-    assert not build.stale(build.POSE_OUT) and build.stale(build.OUT) and build.stale(build.EVAL_OUT)
-    monkeypatch.undo()
-    assert not build.needs_build()
 
 
 def test_python_layer_rejects_host_tensors_and_few_points():

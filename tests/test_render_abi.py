@@ -1,26 +1,15 @@
 """CPU-side checks of libpvrender.so (include/pvrender.h): it builds for gfx950, exports exactly its
-header, rejects bad arguments on the host, and leaves the other three libraries as they were."""
+header, and rejects bad arguments on the host."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.test_build_table import exported, header_functions
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def header_functions(name):
-    src = open(os.path.join(REPO, "include", name)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(pv_[A-Za-z0-9_]+)\s*\(", src)))
-
-
-def exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    return {n for n in names if not re.fullmatch(r"__hip_cuid_[0-9a-f]+", n)}
 
 
 @pytest.fixture(scope="module")
@@ -32,19 +21,20 @@ def lib():
 
 def test_library_builds_for_gfx950(lib):
     from pvnet_amd import build
-    assert build.RENDER_OUT == os.path.join(REPO, "pvnet_amd", "libpvrender.so")
-    assert build.RENDER_HDR == os.path.join(REPO, "include", "pvrender.h")
-    assert [os.path.basename(s) for s in build.RENDER_SRCS] == ["pvrender.hip"]
-    assert set(build.RENDER_DEPS) == {*build.RENDER_SRCS, build.RENDER_HDR}
-    assert b"gfx950" in open(build.RENDER_OUT, "rb").read()
-    assert build.build() == build.OUT and not build.needs_build()
+    render = build.LIBS["render"]
+    assert render.out == os.path.join(REPO, "pvnet_amd", "libpvrender.so")
+    assert render.hdr == os.path.join(REPO, "include", "pvrender.h")
+    assert [os.path.basename(s) for s in render.srcs] == ["pvrender.hip"]
+    assert set(build.closure(render.srcs)) == {*render.srcs, render.hdr}
+    assert b"gfx950" in open(render.out, "rb").read()
+    assert build.build() == build.LIBS["vote"].out and not build.needs_build()
 
 
 def test_exports_exactly_the_header(lib):
     from pvnet_amd import build, _render_lib
     names = header_functions("pvrender.h")
     assert names == ["pv_render_labels", "pv_render_workspace_size", "pv_vertex_field"]
-    assert exported(build.RENDER_OUT) == set(names)
+    assert exported(build.LIBS["render"].out) == set(names)
     bound = {n for n, _, _ in _render_lib.SIGNATURES}
     assert bound == set(names)
     for n in names:
@@ -183,40 +173,6 @@ def test_field_argument_errors_without_device(lib):
     assert call(desc(keypoints=264)) == P.PV_EALIGN and call(desc(vertex=258)) == P.PV_EALIGN
     assert call(desc(b=0)) == 0 and call(desc(b=0, label=None, keypoints=None, vertex=None)) == 0
     assert call(desc(b=0, vn=0)) == P.PV_EINVAL
-
-
-def test_other_libraries_are_undisturbed(lib, monkeypatch):
-    """The other three libraries export what their own pinned tests expect, and the staleness
-    matrix: an edit to the render sources makes only libpvrender.so stale, an edit to the others'
-    sources does not touch it."""
-    from pvnet_amd import build
-    from tests.test_abi import OTHER_EXPORTS, PV_EXPORTS
-    assert exported(build.OUT) == set(PV_EXPORTS) | OTHER_EXPORTS
-    assert exported(build.EVAL_OUT) == {"pv_eval_workspace_size", "pv_nearest_point_idx", "pv_pose_metrics"}
-    assert exported(build.POSE_OUT) == {"pv_epnp", "pv_rt6_to_Rt"}
-    others = set(build.SRCS) | set(build.EVAL_SRCS) | set(build.POSE_DEPS) | {build.HDR, build.EVAL_HDR}
-    assert not set(build.RENDER_DEPS) & others
-    outs = (build.OUT, build.EVAL_OUT, build.POSE_OUT, build.RENDER_OUT)
-    # an edit is simulated by the modification times stale() sees; no file is touched
-    real = os.path.getmtime
-    newest = max(real(p) for p in outs) + 10
-
-    def stale_after(paths):
-        monkeypatch.setattr(build.os.path, "getmtime", lambda p: newest if p in paths else real(p))
-        return tuple(build.stale(o) for o in outs)
-
-    assert stale_after(set(build.RENDER_DEPS)) == (False, False, False, True)
-    assert stale_after({build.RENDER_HDR}) == (False, False, False, True)
-    assert stale_after(others) == (True, True, True, False)
-    assert stale_after(set(build.POSE_DEPS)) == (False, False, True, False)
-    assert stale_after({*build.EVAL_SRCS, build.EVAL_HDR}) == (False, True, False, False)
-    assert stale_after(set(build.SRCS)) == (True, False, False, False)
-    # the headers every translation unit of the other three shares
-    shared = {os.path.join(build.CSRC, "pv_common.h"), os.path.join(build.CSRC, "pv_host.h")}
-    assert stale_after(shared)[3] is False
-    assert stale_after({build.__file__}) == (True, True, True, True)
-    monkeypatch.undo()
-    assert not build.needs_build()
 
 
 def test_python_layer_rejects_before_any_call():

@@ -13,7 +13,7 @@ from pvnet_amd import build as B  # noqa: E402
 
 tu = sys.argv[2] if len(sys.argv) > 2 else "pvvote.hip"
 path = tu if tu.endswith(".s") else os.path.join(B.CSRC, os.path.splitext(tu)[0] + ".gfx950.s")
-if not tu.endswith(".s") and B.stale(path):
+if not tu.endswith(".s") and B.older(path, (*B.closure([os.path.join(B.CSRC, tu)]), B.__file__)):
     B.asm(tu)
 s = open(path).read().split("\n")
 key = sys.argv[1]

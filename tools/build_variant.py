@@ -9,7 +9,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pvnet_amd import build as B  # noqa: E402
 
 name, extra = sys.argv[1], sys.argv[2:]
-srcs = list(B.SRCS)
+srcs = list(B.LIBS["vote"].srcs)
 # --src=NAME.hip:ALT.hip builds with ALT in place of csrc/NAME.hip (e.g. a saved older version)
 for e in [e for e in extra if e.startswith("--src=")]:
     k, alt = e[len("--src="):].split(":")
