@@ -18,9 +18,10 @@
  * transforms.  The photometric steps run in the FIXED order brightness, contrast, saturation, hue;
  * torchvision's ColorJitter shuffles the order per call.
  *
- * Not in scope: Gaussian blur, additive noise, flips (they change the handedness of the pose, so
- * the keypoints of a flipped image belong to no rigid pose of the model), occlusion pasting, and
- * reading or decoding files.
+ * Not in this header: Gaussian blur, additive noise and occlusion pasting, which are pvcompose.h's
+ * (a library of its own, whose draw numbers start after PV_AUG_DRAWS).  Not in scope anywhere: flips
+ * (they change the handedness of the pose, so the keypoints of a flipped image belong to no rigid
+ * pose of the model), and reading or decoding files.
  *
  * Conventions (those of pvvote.h, pveval.h, pvpose.h, pvrender.h, pvmodel.h and pvloss.h):
  *   - pointers are device pointers unless a comment says host;

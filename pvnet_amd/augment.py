@@ -13,7 +13,8 @@ per image of a batch.
 The map is a rotation about the foreground's centroid, a scale, and a shift of the centroid to a
 drawn target: ``rotate_instance``, ``crop_resize_instance_v1`` and ``crop_or_padding_to_fixed_size``
 folded into one resampling.  It is a different parametrisation, not a replay of the reference's
-random stream.  Blur, noise, flips, occlusion pasting and file reading are not here.
+random stream.  Blur, noise and occlusion pasting are ``pvnet_amd.compose``'s (include/pvcompose.h);
+flips and file reading are not in this package.
 
 Nothing is read back and nothing synchronises, so a call can be captured into a graph; the draws
 depend on a device ``state`` = (seed, first sample index) that the caller advances.  No CPU
