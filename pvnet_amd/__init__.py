@@ -5,7 +5,8 @@ loss (pvnet_amd/net_utils.py) and the training augmentation (pvnet_amd/augment.p
 stays as cheap as it was.  The augmentation's hot-path entry point keeps its module's name in
 front of it, ``pvnet_amd.augment.apply``: a bare ``apply`` at package level would say nothing.  So do
 the frame composition's two (pvnet_amd/compose.py): ``pvnet_amd.compose.compose`` and
-``pvnet_amd.compose.finish``; the rest of that module is exported here."""
+``pvnet_amd.compose.finish``; the rest of that module is exported here.  The optimiser step
+(pvnet_amd/optim.py) exports its one class, ``Optimizer``."""
 
 _RENDER = ("MeshTable", "render_labels", "vertex_field", "render_ground_truth", "mask_iou")
 _MODELS = ("extent", "farthest_points", "diameter", "corners_3d", "keypoints_3d")
@@ -13,7 +14,8 @@ _LOSS = ("pvnet_loss",)
 _AUGMENT = ("AugmentParams", "label_stats", "random_params", "transform_keypoints", "augment_ground_truth")
 _COMPOSE = ("Placement", "make_picks", "random_placement", "shift_keypoints", "shift_camera", "visible_fraction",
             "compose_ground_truth")
-__all__ = [*_RENDER, *_MODELS, *_LOSS, *_AUGMENT, *_COMPOSE]
+_OPTIM = ("Optimizer",)
+__all__ = [*_RENDER, *_MODELS, *_LOSS, *_AUGMENT, *_COMPOSE, *_OPTIM]
 
 
 def __getattr__(name):
@@ -32,4 +34,7 @@ def __getattr__(name):
     if name in _COMPOSE:
         from . import compose
         return getattr(compose, name)
+    if name in _OPTIM:
+        from . import optim
+        return getattr(optim, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,4 +1,4 @@
-"""Build the HIP C-ABI libraries (the tables LIBS and MORE_LIBS) in-tree for gfx950.
+"""Build the HIP C-ABI libraries (the tables LIBS, MORE_LIBS and LATER_LIBS) in-tree for gfx950.
 
     python -m pvnet_amd.build            # or __graft_entry__.build()
 
@@ -56,6 +56,12 @@ LIBS = {
 MORE_LIBS = {
     "compose": _lib("pvcompose", "pvcompose.hip"),
 }
+# and again: the optimiser-step library (include/pvoptim.h), one translation unit that includes no
+# other file of csrc/.  A third table only because tests/test_compose_abi.py holds MORE_LIBS to its
+# one row as tests/test_build_table.py holds LIBS to seven; a later library goes here.
+LATER_LIBS = {
+    "optim": _lib("pvoptim", "pvoptim.hip"),
+}
 ARCH = os.environ.get("PVVOTE_ARCH", "gfx950")
 
 HIPCC_FLAGS = [
@@ -77,6 +83,11 @@ HIPCC_FLAGS = [
     "-mllvm", "-amdgpu-mfma-vgpr-form=1",
     "-Wall",
 ]
+
+
+def libs() -> list:
+    """Every library of the three tables, in build order."""
+    return [*LIBS.values(), *MORE_LIBS.values(), *LATER_LIBS.values()]
 
 
 def hipcc() -> str:
@@ -113,14 +124,14 @@ def older(path: str, deps) -> bool:
 
 def stale(out: str) -> bool:
     """Is the library `out` missing, or older than a file the compiler reads for it or this file?"""
-    srcs = {lib.out: lib.srcs for lib in (*LIBS.values(), *MORE_LIBS.values())}
+    srcs = {lib.out: lib.srcs for lib in libs()}
     if out not in srcs:
-        raise ValueError(f"{out} is not a library of LIBS or MORE_LIBS; for another file use older(path, deps)")
+        raise ValueError(f"{out} is not a library of LIBS, MORE_LIBS or LATER_LIBS; for another file use older(path, deps)")
     return older(out, (*closure(srcs[out]), __file__))
 
 
 def needs_build() -> bool:
-    return any(stale(lib.out) for lib in (*LIBS.values(), *MORE_LIBS.values()))
+    return any(stale(lib.out) for lib in libs())
 
 
 def _link(out: str, srcs, extra=()) -> None:
@@ -133,8 +144,8 @@ def _link(out: str, srcs, extra=()) -> None:
 
 
 def build(force: bool = False, extra=()) -> str:
-    """Build every library of LIBS and MORE_LIBS (each when stale); returns libpvvote.so's path."""
-    for lib in (*LIBS.values(), *MORE_LIBS.values()):
+    """Build every library of the three tables (each when stale); returns libpvvote.so's path."""
+    for lib in libs():
         if force or stale(lib.out):
             _link(lib.out, lib.srcs, extra)
     return LIBS["vote"].out
