@@ -1,4 +1,4 @@
-"""Build the HIP C-ABI libraries (the tables LIBS, MORE_LIBS and LATER_LIBS) in-tree for gfx950.
+"""Build the HIP C-ABI libraries (the tables LIBS, MORE_LIBS, LATER_LIBS and NEXT_LIBS) in-tree for gfx950.
 
     python -m pvnet_amd.build            # or __graft_entry__.build()
 
@@ -62,6 +62,12 @@ MORE_LIBS = {
 LATER_LIBS = {
     "optim": _lib("pvoptim", "pvoptim.hip"),
 }
+# and once more: the colour-render library (include/pvshade.h), one translation unit that includes no
+# other file of csrc/.  A fourth table only because tests/test_optim_abi.py holds libs() to the nine
+# above, with the optimiser last; all_libs() is what build(), stale() and needs_build() work over.
+NEXT_LIBS = {
+    "shade": _lib("pvshade", "pvshade.hip"),
+}
 ARCH = os.environ.get("PVVOTE_ARCH", "gfx950")
 
 HIPCC_FLAGS = [
@@ -88,6 +94,11 @@ HIPCC_FLAGS = [
 def libs() -> list:
     """Every library of the three tables, in build order."""
     return [*LIBS.values(), *MORE_LIBS.values(), *LATER_LIBS.values()]
+
+
+def all_libs() -> list:
+    """Every library that is built: libs() and the fourth table, in build order."""
+    return [*libs(), *NEXT_LIBS.values()]
 
 
 def hipcc() -> str:
@@ -124,14 +135,15 @@ def older(path: str, deps) -> bool:
 
 def stale(out: str) -> bool:
     """Is the library `out` missing, or older than a file the compiler reads for it or this file?"""
-    srcs = {lib.out: lib.srcs for lib in libs()}
+    srcs = {lib.out: lib.srcs for lib in all_libs()}
     if out not in srcs:
-        raise ValueError(f"{out} is not a library of LIBS, MORE_LIBS or LATER_LIBS; for another file use older(path, deps)")
+        raise ValueError(f"{out} is not a library of LIBS, MORE_LIBS, LATER_LIBS or NEXT_LIBS; for another file use "
+                         "older(path, deps)")
     return older(out, (*closure(srcs[out]), __file__))
 
 
 def needs_build() -> bool:
-    return any(stale(lib.out) for lib in libs())
+    return any(stale(lib.out) for lib in all_libs())
 
 
 def _link(out: str, srcs, extra=()) -> None:
@@ -144,8 +156,8 @@ def _link(out: str, srcs, extra=()) -> None:
 
 
 def build(force: bool = False, extra=()) -> str:
-    """Build every library of the three tables (each when stale); returns libpvvote.so's path."""
-    for lib in libs():
+    """Build every library of the four tables (each when stale); returns libpvvote.so's path."""
+    for lib in all_libs():
         if force or stale(lib.out):
             _link(lib.out, lib.srcs, extra)
     return LIBS["vote"].out
