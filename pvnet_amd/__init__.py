@@ -6,7 +6,9 @@ stays as cheap as it was.  The augmentation's hot-path entry point keeps its mod
 front of it, ``pvnet_amd.augment.apply``: a bare ``apply`` at package level would say nothing.  So do
 the frame composition's two (pvnet_amd/compose.py): ``pvnet_amd.compose.compose`` and
 ``pvnet_amd.compose.finish``; the rest of that module is exported here.  The optimiser step
-(pvnet_amd/optim.py) exports its one class, ``Optimizer``."""
+(pvnet_amd/optim.py) exports its one class, ``Optimizer``.  Scoring in the BOP Challenge's terms
+(pvnet_amd/bop.py) exports its table, its two error entries and the average recall.  ``vsd`` and
+``sym_errors`` are functions, so ``pvnet_amd.bop`` the module stays reachable under its own name."""
 
 _RENDER = ("MeshTable", "render_labels", "vertex_field", "render_ground_truth", "mask_iou")
 _MODELS = ("extent", "farthest_points", "diameter", "corners_3d", "keypoints_3d")
@@ -15,7 +17,8 @@ _AUGMENT = ("AugmentParams", "label_stats", "random_params", "transform_keypoint
 _COMPOSE = ("Placement", "make_picks", "random_placement", "shift_keypoints", "shift_camera", "visible_fraction",
             "compose_ground_truth")
 _OPTIM = ("Optimizer",)
-__all__ = [*_RENDER, *_MODELS, *_LOSS, *_AUGMENT, *_COMPOSE, *_OPTIM]
+_BOP = ("SymmetryTable", "sym_errors", "vsd", "average_recall")
+__all__ = [*_RENDER, *_MODELS, *_LOSS, *_AUGMENT, *_COMPOSE, *_OPTIM, *_BOP]
 
 
 def __getattr__(name):
@@ -37,4 +40,7 @@ def __getattr__(name):
     if name in _OPTIM:
         from . import optim
         return getattr(optim, name)
+    if name in _BOP:
+        from . import bop
+        return getattr(bop, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

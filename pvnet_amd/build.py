@@ -1,4 +1,4 @@
-"""Build the HIP C-ABI libraries (the tables LIBS, MORE_LIBS, LATER_LIBS and NEXT_LIBS) in-tree for gfx950.
+"""Build the HIP C-ABI libraries (the tables LIBS, MORE_LIBS, LATER_LIBS, NEXT_LIBS and BOP_LIBS) in-tree for gfx950.
 
     python -m pvnet_amd.build            # or __graft_entry__.build()
 
@@ -68,6 +68,12 @@ LATER_LIBS = {
 NEXT_LIBS = {
     "shade": _lib("pvshade", "pvshade.hip"),
 }
+# and a fifth: the BOP pose-error library (include/pvbop.h), one translation unit that includes no
+# other file of csrc/.  A table of its own only because tests/test_shade_abi.py holds all_libs() to
+# the ten above, with shade last; every_lib() is what build(), stale() and needs_build() work over.
+BOP_LIBS = {
+    "bop": _lib("pvbop", "pvbop.hip"),
+}
 ARCH = os.environ.get("PVVOTE_ARCH", "gfx950")
 
 HIPCC_FLAGS = [
@@ -97,8 +103,13 @@ def libs() -> list:
 
 
 def all_libs() -> list:
-    """Every library that is built: libs() and the fourth table, in build order."""
+    """libs() and the fourth table, in build order."""
     return [*libs(), *NEXT_LIBS.values()]
+
+
+def every_lib() -> list:
+    """Every library that is built: all_libs() and the fifth table, in build order."""
+    return [*all_libs(), *BOP_LIBS.values()]
 
 
 def hipcc() -> str:
@@ -135,15 +146,15 @@ def older(path: str, deps) -> bool:
 
 def stale(out: str) -> bool:
     """Is the library `out` missing, or older than a file the compiler reads for it or this file?"""
-    srcs = {lib.out: lib.srcs for lib in all_libs()}
+    srcs = {lib.out: lib.srcs for lib in every_lib()}
     if out not in srcs:
-        raise ValueError(f"{out} is not a library of LIBS, MORE_LIBS, LATER_LIBS or NEXT_LIBS; for another file use "
+        raise ValueError(f"{out} is not a library of LIBS, MORE_LIBS, LATER_LIBS, NEXT_LIBS or BOP_LIBS; for another file use "
                          "older(path, deps)")
     return older(out, (*closure(srcs[out]), __file__))
 
 
 def needs_build() -> bool:
-    return any(stale(lib.out) for lib in all_libs())
+    return any(stale(lib.out) for lib in every_lib())
 
 
 def _link(out: str, srcs, extra=()) -> None:
@@ -156,8 +167,8 @@ def _link(out: str, srcs, extra=()) -> None:
 
 
 def build(force: bool = False, extra=()) -> str:
-    """Build every library of the four tables (each when stale); returns libpvvote.so's path."""
-    for lib in all_libs():
+    """Build every library of the five tables (each when stale); returns libpvvote.so's path."""
+    for lib in every_lib():
         if force or stale(lib.out):
             _link(lib.out, lib.srcs, extra)
     return LIBS["vote"].out

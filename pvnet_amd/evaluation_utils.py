@@ -247,6 +247,13 @@ class Evaluator:
         Rt = pose_from_voting(mean, cov, p3, K)
         return self._score(Rt, pose_targets, mid, K)
 
+    def bop_errors(self, pose_pred, pose_targets, syms, K, model_id=None, metrics=("mssd", "mspd")):
+        """MSSD and MSPD of poses against this evaluator's table (``pvnet_amd.bop.sym_errors``; syms is a
+        ``pvnet_amd.bop.SymmetryTable``).  Records nothing: the recorders keep the 2018 protocol."""
+        from . import bop
+        pose_gt = torch.as_tensor(pose_targets).to(self.table.device)
+        return bop.sym_errors(pose_pred, pose_gt, self.table, syms, K, model_id, metrics)
+
     def average_precision(self, verbose: bool = False):
         """(projection 2-D, ADD, 5 cm 5 deg) hit rates over everything recorded so far: the one
         host readback of the evaluation."""
