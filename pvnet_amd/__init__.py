@@ -8,7 +8,9 @@ the frame composition's two (pvnet_amd/compose.py): ``pvnet_amd.compose.compose`
 ``pvnet_amd.compose.finish``; the rest of that module is exported here.  The optimiser step
 (pvnet_amd/optim.py) exports its one class, ``Optimizer``.  Scoring in the BOP Challenge's terms
 (pvnet_amd/bop.py) exports its table, its two error entries and the average recall.  ``vsd`` and
-``sym_errors`` are functions, so ``pvnet_amd.bop`` the module stays reachable under its own name."""
+``sym_errors`` are functions, so ``pvnet_amd.bop`` the module stays reachable under its own name.  Depth
+pose refinement (pvnet_amd/icp.py) exports ``refine_depth``; ``pvnet_amd.icp.iterate`` and
+``pvnet_amd.icp.linearise`` keep the module's name in front of them."""
 
 _RENDER = ("MeshTable", "render_labels", "vertex_field", "render_ground_truth", "mask_iou")
 _MODELS = ("extent", "farthest_points", "diameter", "corners_3d", "keypoints_3d")
@@ -18,7 +20,8 @@ _COMPOSE = ("Placement", "make_picks", "random_placement", "shift_keypoints", "s
             "compose_ground_truth")
 _OPTIM = ("Optimizer",)
 _BOP = ("SymmetryTable", "sym_errors", "vsd", "average_recall")
-__all__ = [*_RENDER, *_MODELS, *_LOSS, *_AUGMENT, *_COMPOSE, *_OPTIM, *_BOP]
+_ICP = ("refine_depth",)
+__all__ = [*_RENDER, *_MODELS, *_LOSS, *_AUGMENT, *_COMPOSE, *_OPTIM, *_BOP, *_ICP]
 
 
 def __getattr__(name):
@@ -43,4 +46,7 @@ def __getattr__(name):
     if name in _BOP:
         from . import bop
         return getattr(bop, name)
+    if name in _ICP:
+        from . import icp
+        return getattr(icp, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

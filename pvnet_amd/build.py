@@ -1,4 +1,4 @@
-"""Build the HIP C-ABI libraries (the tables LIBS, MORE_LIBS, LATER_LIBS, NEXT_LIBS and BOP_LIBS) in-tree for gfx950.
+"""Build the HIP C-ABI libraries (the tables LIBS, MORE_LIBS, LATER_LIBS, NEXT_LIBS, BOP_LIBS and ICP_LIBS) in-tree for gfx950.
 
     python -m pvnet_amd.build            # or __graft_entry__.build()
 
@@ -70,9 +70,15 @@ NEXT_LIBS = {
 }
 # and a fifth: the BOP pose-error library (include/pvbop.h), one translation unit that includes no
 # other file of csrc/.  A table of its own only because tests/test_shade_abi.py holds all_libs() to
-# the ten above, with shade last; every_lib() is what build(), stale() and needs_build() work over.
+# the ten above, with shade last.
 BOP_LIBS = {
     "bop": _lib("pvbop", "pvbop.hip"),
+}
+# and a sixth: the depth-refinement library (include/pvicp.h), one translation unit that includes no
+# other file of csrc/.  A table of its own only because tests/test_bop_abi.py holds every_lib() to the
+# eleven above, with bop last; each_lib() is what build(), stale() and needs_build() work over.
+ICP_LIBS = {
+    "icp": _lib("pvicp", "pvicp.hip"),
 }
 ARCH = os.environ.get("PVVOTE_ARCH", "gfx950")
 
@@ -108,8 +114,13 @@ def all_libs() -> list:
 
 
 def every_lib() -> list:
-    """Every library that is built: all_libs() and the fifth table, in build order."""
+    """all_libs() and the fifth table, in build order."""
     return [*all_libs(), *BOP_LIBS.values()]
+
+
+def each_lib() -> list:
+    """Every library that is built: every_lib() and the sixth table, in build order."""
+    return [*every_lib(), *ICP_LIBS.values()]
 
 
 def hipcc() -> str:
@@ -146,15 +157,15 @@ def older(path: str, deps) -> bool:
 
 def stale(out: str) -> bool:
     """Is the library `out` missing, or older than a file the compiler reads for it or this file?"""
-    srcs = {lib.out: lib.srcs for lib in every_lib()}
+    srcs = {lib.out: lib.srcs for lib in each_lib()}
     if out not in srcs:
-        raise ValueError(f"{out} is not a library of LIBS, MORE_LIBS, LATER_LIBS, NEXT_LIBS or BOP_LIBS; for another file use "
-                         "older(path, deps)")
+        raise ValueError(f"{out} is not a library of LIBS, MORE_LIBS, LATER_LIBS, NEXT_LIBS, BOP_LIBS or ICP_LIBS; for another "
+                         "file use older(path, deps)")
     return older(out, (*closure(srcs[out]), __file__))
 
 
 def needs_build() -> bool:
-    return any(stale(lib.out) for lib in every_lib())
+    return any(stale(lib.out) for lib in each_lib())
 
 
 def _link(out: str, srcs, extra=()) -> None:
@@ -167,8 +178,8 @@ def _link(out: str, srcs, extra=()) -> None:
 
 
 def build(force: bool = False, extra=()) -> str:
-    """Build every library of the five tables (each when stale); returns libpvvote.so's path."""
-    for lib in every_lib():
+    """Build every library of the six tables (each when stale); returns libpvvote.so's path."""
+    for lib in each_lib():
         if force or stale(lib.out):
             _link(lib.out, lib.srcs, extra)
     return LIBS["vote"].out

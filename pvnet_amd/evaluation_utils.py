@@ -254,6 +254,12 @@ class Evaluator:
         pose_gt = torch.as_tensor(pose_targets).to(self.table.device)
         return bop.sym_errors(pose_pred, pose_gt, self.table, syms, K, model_id, metrics)
 
+    def refine_depth(self, pose_pred, model_id, depth, K, mesh_table, **kw):
+        """Refine poses against the sensor's depth before they are scored (``pvnet_amd.icp.refine_depth``;
+        mesh_table is a ``pvnet_amd.render.MeshTable``) -> (poses f64 [b, 3, 4], info).  Records nothing."""
+        from . import icp
+        return icp.refine_depth(mesh_table, pose_pred, model_id, depth, K, **kw)
+
     def average_precision(self, verbose: bool = False):
         """(projection 2-D, ADD, 5 cm 5 deg) hit rates over everything recorded so far: the one
         host readback of the evaluation."""
